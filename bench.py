@@ -17,7 +17,11 @@ grows. Launch modes for N>1 (one rank per GPU over RCCL):
 
 Each step is a full training step: synthetic batch already on the device, forward,
 cross-entropy, backward with bucketed RCCL all-reduce overlapped with backward (xddp Reducer),
-fused SGD (momentum 0.9, wd 1e-4, fp32 master weights) — nothing skipped. Besides the headline
+fused SGD (momentum 0.9, wd 1e-4, fp32 master weights) — nothing skipped. A plain run does only
+that: set up, warm up, time the K steps, print the result line (``--dump-outputs DIR`` also writes
+the last timed step's loss, logits, gradients and updated parameters as ``DIR/<name>.npy``; the
+inputs are seeded, so two builds can be compared output for output). With ``--full`` the ranks'
+replicas are checked after the timed steps (exit 3 when they diverged) and besides the headline
 number the JSON reports what the communicator saw (``nranks``), the rebuilt bucket layout, the
 Reducer's sampled backward comm / overlap times (measured AFTER the timed region, in extra
 diagnostic steps, so the timed loop is untouched), the achieved all-reduce bus bandwidth per
@@ -113,7 +117,17 @@ def parse(argv=None):
                     help="fp32: MIOpen's implicit-GEMM conv solvers off (fp32-accurate weight gradients, but the "
                          "channels_last fallback runs ~6x slower; utils/precision.py)")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the replica check "
+                         "(exit 3 when the ranks' parameters differ), the comm diagnostics (extra untimed steps, "
+                         "bucket layout, all-reduce bus bandwidth at N>1) and the model-FLOPs count behind "
+                         "model_tflops_per_gpu / mfu. Off: set up, warm up, time the steps, print the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32): "
+                         "its loss, its logits, and the gradients and updated parameters it left (see dump_outputs)")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.recipe == "reference":
         a.dtype, a.optimizer, a.lr, a.momentum, a.weight_decay, a.lr_warmup = "fp32", "sgd", 0.01, 0.0, 0.0, 0
     if a.batch_size is None:
@@ -506,6 +520,8 @@ def main(argv=None):
             grp["lr"] = lr * f
         n_opt_steps[0] += 1
 
+    last_out = [None]  # --dump-outputs: the last step's logits
+
     def step():
         if graphed is None:
             set_lr()
@@ -515,7 +531,11 @@ def main(argv=None):
         for i in range(micro - 1):
             with ddp.no_sync():
                 loss_fn(ddp(xs[i]), ys[i]).backward()
-        loss = loss_fn(ddp(xs[-1]), ys[-1])
+        out = ddp(xs[-1])
+        if args.dump_outputs:
+            last_out[0] = out.detach()  # (a reference: no copy, no sync)
+        loss = loss_fn(out, ys[-1])
+        del out
         loss.backward()
         if not overlap:  # (overlapped: every bucket was stepped during backward)
             opt.step()
@@ -553,11 +573,15 @@ def main(argv=None):
     loss_min, loss_max = float(lt.min()), float(lt.max())
     del traj
 
-    # ---------------- replica check (outside the timed region): every rank's parameters and
+    if args.dump_outputs and rank == 0:  # before anything below steps the model again
+        dump_outputs(args.dump_outputs, loss, last_out[0], ddp)
+    last_out[0] = None
+
+    # ---------------- replica check (--full; outside the timed region): every rank's parameters and
     # buffers must be bit-identical after the timed steps (utils/replicas.py); a diverged run exits
     # non-zero and names the ranks
     replicas = None
-    if args.impl == "xddp":
+    if args.full and args.impl == "xddp":
         if ddp.will_sync_module_buffers():
             ddp._sync_buffers()  # BN running stats took local updates in the last forward
         replicas = ddp.check_replicas(max_diff=world > 1)
@@ -565,9 +589,9 @@ def main(argv=None):
             print(f"[bench] rank {rank}: REPLICAS DIVERGED: ranks {replicas['mismatch_ranks']} disagree with the "
                   f"majority (max |param - rank0 param| = {replicas['max_abs_diff']})", file=sys.stderr, flush=True)
 
-    # ---------------- diagnostics (outside the timed region)
+    # ---------------- diagnostics (--full; outside the timed region)
     diag = {}
-    if args.impl == "xddp" and replicas["replicas_identical"]:
+    if args.full and args.impl == "xddp" and replicas["replicas_identical"]:
         diag = diagnostics(args, ddp, step, sync, dist, device, world, overlap)
 
     ms = elapsed / args.steps * 1e3
@@ -575,7 +599,7 @@ def main(argv=None):
     units = per_step_samples * args.steps * (args.seq_len if is_lm(args) else 1)
     value = units / elapsed
     if rank == 0:
-        flops = train_flops_per_sample(args)
+        flops = train_flops_per_sample(args) if args.full else None
         if args.model == "resnet50":
             metric = "images/sec (whole node) ResNet-50 DDP at 1/2/4/8 MI355X; scaling efficiency"
         elif is_lm(args):
@@ -662,6 +686,45 @@ def main(argv=None):
     if replicas is not None and not replicas["replicas_identical"]:
         return REPLICA_DIVERGED  # every rank: the run's parameters diverged (see the JSON line / stderr)
     return 0
+
+
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MB of float32, so loss + logits + grads + params stay under 64 MB
+
+
+def dump_outputs(path, loss, logits, ddp):
+    """``--dump-outputs``: what the last timed step handed back, as float32 ``.npy`` files under
+    ``path``: ``loss`` (scalar), ``logits`` (the forward's output; absent under ``--graphs``, whose
+    replayed step returns the loss alone), ``grads`` and ``params`` (every parameter's gradient as the
+    step left it, and its updated value, flattened in ``named_parameters`` order and concatenated).
+    An array over DUMP_MAX_ELEMS elements is cut to a fixed sample: indices drawn on the CPU from a
+    seeded generator, per tensor in proportion to its size, so two builds dump the same elements."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(device="cpu", dtype=torch.float32).numpy())
+
+    def sample(flat, keep, seed):
+        if keep >= flat.numel():
+            return flat
+        idx = torch.randint(0, flat.numel(), (keep,), generator=torch.Generator().manual_seed(seed))
+        return flat[idx.sort().values.to(flat.device)]
+
+    save("loss", loss.reshape(()))
+    if logits is not None:
+        save("logits", sample(logits.reshape(-1), DUMP_MAX_ELEMS, 0))
+    params = [p for _, p in ddp.module.named_parameters()]
+    total = sum(p.numel() for p in params)
+    grads, values = [], []
+    for i, p in enumerate(params):
+        keep = p.numel() if total <= DUMP_MAX_ELEMS else max(1, p.numel() * DUMP_MAX_ELEMS // total)
+        g = p.grad if p.grad is not None else torch.zeros_like(p)
+        grads.append(sample(g.detach().reshape(-1), keep, 1 + i).float())
+        values.append(sample(p.detach().reshape(-1), keep, 1 + i).float())
+    save("grads", torch.cat(grads))
+    save("params", torch.cat(values))
 
 
 def diagnostics(args, ddp, step, sync, dist, device, world, overlap=False):

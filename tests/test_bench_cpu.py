@@ -11,13 +11,13 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(extra_env=None, args=(), gpus=2):
+def _run(extra_env=None, args=(), gpus=2, full=True):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     env.update(extra_env or {})
     return subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(gpus), "--device", "cpu",
-                           "--model", "mlp", "--steps", "3", "--warmup", "2", *args],
+                           "--model", "mlp", "--steps", "3", "--warmup", "2", *(["--full"] if full else []), *args],
                           capture_output=True, text=True, timeout=240, env=env, cwd="/tmp")
 
 
@@ -65,6 +65,66 @@ def test_one_rank_reports_no_comm():
     assert c["avg_backward_compute_ms"] is not None and c["timed_iterations"] >= 2
     assert "allreduce_busbw" not in d and "warning" not in d
     assert d["buckets"]["tail"]["exposed_tail_us_model"] == 0.0
+
+
+def test_plain_run_reports_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full: no replica check, diagnostics or flop count, the same headline fields; the
+    dumped outputs of the last timed step are float32 and the same from run to run (seeded inputs)."""
+    import numpy as np
+
+    dumps = {}
+    for name in ("a", "b"):
+        r = _run(gpus=1, full=False, args=("--dump-outputs", str(tmp_path / name)))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["unit"] == "images/s" and d["higher_is_better"] is True and d["dtype"] == "fp32"
+        assert d["value"] == pytest.approx(64 * 1e3 / d["ms_per_step"], rel=1e-3)
+        for k in ("comm", "buckets", "nranks", "comm_info", "mfu", "model_tflops_per_gpu"):
+            assert k not in d, k
+        assert d["replicas_identical"] is None
+        dumps[name] = {f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+        assert sorted(dumps[name]) == ["grads", "logits", "loss", "params"]
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in dumps[name].values())
+        assert sum(v.nbytes for v in dumps[name].values()) <= 64 << 20
+        assert float(dumps[name]["loss"]) == pytest.approx(d["final_loss"], abs=1e-4)
+    a, b = dumps["a"], dumps["b"]
+    assert a["loss"].shape == () and a["logits"].shape == (64 * 10,) and a["grads"].shape == a["params"].shape
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
+    assert np.abs(a["grads"]).max() > 0 and np.abs(a["params"]).max() > 0
+
+
+def test_dump_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """Outputs over the size limit are cut to the same seeded sample on every call."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(64, 100), torch.nn.Linear(100, 7))
+    logits = m(torch.randn(300, 64))
+    logits.sum().backward()
+
+    class Wrapped:
+        module = m
+
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), logits.sum(), logits.detach(), Wrapped)
+    a = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    for f, v in a.items():
+        np.testing.assert_array_equal(v, np.load(tmp_path / "b" / f))
+    assert a["logits.npy"].shape == (1000,) and set(a["logits.npy"]) <= set(logits.detach().reshape(-1).numpy())
+    # per tensor in proportion to its size (at least one element each), in named_parameters order
+    total = sum(p.numel() for p in m.parameters())
+    keep = [max(1, p.numel() * 1000 // total) for p in m.parameters()]
+    assert a["params.npy"].shape == a["grads.npy"].shape == (sum(keep),)
+    assert set(a["params.npy"][keep[0]:keep[0] + keep[1]]) <= set(m[0].bias.detach().numpy())
 
 
 def test_flop_count_per_sample_matches_survey():

@@ -71,7 +71,8 @@ def test_bench_reports_replica_divergence(corrupt):
     if corrupt:
         env["XDDP_FAULT_CORRUPT"] = "rank=1,iter=3"
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--device", "cpu",
-                        "--backend", "cpu", "--model", "mlp", "--steps", "3", "--warmup", "1", "--diag-steps", "0"],
+                        "--backend", "cpu", "--model", "mlp", "--steps", "3", "--warmup", "1", "--diag-steps", "0",
+                        "--full"],
                        capture_output=True, text=True, env=env, timeout=600, cwd="/tmp")
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])

@@ -39,7 +39,7 @@ def _bench(extra_env):
     env.update(extra_env)
     return subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "peer",
                            "--model", "simplecnn", "--batch-size", "32", "--image-size", "32", "--steps", "4",
-                           "--warmup", "2", "--diag-steps", "0", "--launch-timeout", "200"],
+                           "--warmup", "2", "--diag-steps", "0", "--launch-timeout", "200", "--full"],
                           capture_output=True, text=True, env=env, timeout=240, cwd=REPO)
 
 

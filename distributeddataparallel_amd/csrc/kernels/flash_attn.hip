@@ -162,14 +162,21 @@ __device__ __forceinline__ void dma_tile(const uint16_t* base, int64_t ss, int r
 // WH (whole K/V, non-causal D = 64 with Sk <= 256: ViT's 197 tokens): every K/V tile of the head
 // is DMA'd up front (64 KB of LDS) and the tile loop runs without barriers; waves whose 32 query
 // rows all lie past Sq skip the math.
-template <int D, bool CAUSAL, int NW, bool WH = false>
+// DOC (packed sequences; causal, Sq == Sk): DS[b][q] is the first key of query q's document, and
+// key k is visible iff DS[b][q] <= k <= q. The K/V loop starts at the tile of the block's first
+// row's document, a wave skips the tiles before its first row's document, and only the tiles a
+// document of the wave starts inside take the lower mask. One document per row = the plain causal
+// kernel's tiles, order and masks (bitwise equal results).
+template <int D, bool CAUSAL, int NW, bool WH = false, bool DOC = false>
 __global__ __launch_bounds__(64 * NW, WH && NW == 8 ? 4 : 1) void fa_fwd_kernel(const uint16_t* __restrict__ Q, const uint16_t* __restrict__ K,
                                                         const uint16_t* __restrict__ V, uint16_t* __restrict__ O,
                                                         float* __restrict__ LSE, int Sq, int Sk, int Hq, int Hkv,
                                                         Strides qs, Strides ks, Strides vs, Strides os,
-                                                        float scale_log2, int nqb) {
+                                                        float scale_log2, int nqb,
+                                                        const int* __restrict__ DS) {
   constexpr int KS = D / 16, NT = D / 32, BQ = 32 * NW;
   static_assert(!WH || (!CAUSAL && D == 64), "whole-K/V staging is the non-causal D = 64 form");
+  static_assert(!DOC || CAUSAL, "the document mask is a refinement of the causal one");
   __shared__ __attribute__((aligned(16))) uint8_t KVs[WH ? 4 : 2][2][kBK * D * 2];  // [stage or tile][K, V]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 5;
   const int bh = blockIdx.y, b = bh / Hq, h = bh % Hq, hk = h / (Hq / Hkv);
@@ -177,7 +184,9 @@ __global__ __launch_bounds__(64 * NW, WH && NW == 8 ? 4 : 1) void fa_fwd_kernel(
   const uint16_t* Kb = K + b * ks.b + hk * ks.h;
   const uint16_t* Vb = V + b * vs.b + hk * vs.h;
   // causal: a workgroup takes query blocks (nqb - 1 - x, x) — a heavy and a light one, the same
-  // total number of K/V tiles for every workgroup (one pass when they coincide)
+  // total number of K/V tiles for every workgroup (one pass when they coincide). DOC keeps the
+  // pairing although a block's tile count then depends on where its documents start, so the
+  // workgroups are no longer equal: every one of them still does at most the causal work
   const int npass = CAUSAL && (int)blockIdx.x != nqb - 1 - (int)blockIdx.x ? 2 : 1;
 #pragma unroll 1
   for (int pass = 0; pass < npass; ++pass) {
@@ -200,6 +209,19 @@ __global__ __launch_bounds__(64 * NW, WH && NW == 8 ? 4 : 1) void fa_fwd_kernel(
 
     const int kend = CAUSAL ? min(Sk, q0 + BQ) : Sk;
     const int ntiles = (kend + kBK - 1) / kBK;
+    // DOC: ds = first key of this lane's row's document (clamped to [0, row], so a malformed array
+    // can only give wrong numbers, never move a tile index or a DMA row out of range; rows past Sq
+    // take row Sq - 1's). doc_start is non-decreasing, so the block's first row has the smallest
+    // start and the K/V loop begins at its tile (jbeg); ds_w / ds_l are the wave's first / last row's.
+    int ds = 0, ds_w = 0, ds_l = 0, jbeg = 0;
+    if constexpr (DOC) {
+      const int* DSb = DS + (int64_t)b * Sq;
+      const int r = min(qrow, Sq - 1);
+      ds = min(max(DSb[r], 0), r);
+      ds_w = __builtin_amdgcn_readlane(ds, 0);
+      ds_l = __builtin_amdgcn_readlane(ds, 31);
+      jbeg = min(max(DSb[q0], 0), q0) / kBK;  // q0 < Sq, so jbeg < ntiles
+    }
     if (WH) {
       for (int j = 0; j < ntiles; ++j) {
         dma_tile<D, NW>(Kb, ks.s, j * kBK, Sk, KVs[j][0], w, lane);
@@ -207,21 +229,24 @@ __global__ __launch_bounds__(64 * NW, WH && NW == 8 ? 4 : 1) void fa_fwd_kernel(
       }
       dma_barrier();
     } else {
-      dma_tile<D, NW>(Kb, ks.s, 0, Sk, KVs[0][0], w, lane);
-      dma_tile<D, NW>(Vb, vs.s, 0, Sk, KVs[0][1], w, lane);
+      dma_tile<D, NW>(Kb, ks.s, jbeg * kBK, Sk, KVs[0][0], w, lane);
+      dma_tile<D, NW>(Vb, vs.s, jbeg * kBK, Sk, KVs[0][1], w, lane);
     }
-    for (int j = 0; j < ntiles; ++j) {
+    for (int j = jbeg; j < ntiles; ++j) {
       const int k0 = j * kBK;
+      const int st = DOC ? j - jbeg : j;  // the stage parity counts from the first tile loaded
       if (!WH) {
         dma_barrier();
         if (j + 1 < ntiles) {  // next tile in flight during this tile's math
-          dma_tile<D, NW>(Kb, ks.s, k0 + kBK, Sk, KVs[(j + 1) & 1][0], w, lane);
-          dma_tile<D, NW>(Vb, vs.s, k0 + kBK, Sk, KVs[(j + 1) & 1][1], w, lane);
+          dma_tile<D, NW>(Kb, ks.s, k0 + kBK, Sk, KVs[(st + 1) & 1][0], w, lane);
+          dma_tile<D, NW>(Vb, vs.s, k0 + kBK, Sk, KVs[(st + 1) & 1][1], w, lane);
         }
       }
-      const uint8_t* Kt = KVs[WH ? j : (j & 1)][0];
-      const uint8_t* Vt = KVs[WH ? j : (j & 1)][1];
-      if (WH ? qw < Sq : (!CAUSAL || k0 <= qw + 31)) {  // a wave whose rows all precede the tile skips it
+      const uint8_t* Kt = KVs[WH ? j : (st & 1)][0];
+      const uint8_t* Vt = KVs[WH ? j : (st & 1)][1];
+      // a wave whose rows all precede the tile skips it; DOC: also one whose rows' documents all
+      // start after the tile (wave-uniform: ds_w is the smallest start in the wave)
+      if (WH ? qw < Sq : ((!CAUSAL || k0 <= qw + 31) && (!DOC || k0 + kBK - 1 >= ds_w))) {
         f32x16 sc[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -232,15 +257,24 @@ __global__ __launch_bounds__(64 * NW, WH && NW == 8 ? 4 : 1) void fa_fwd_kernel(
 #pragma unroll
           for (int s2 = 0; s2 < KS; ++s2) sc[t] = mfma32(ld_rowfrag<D>(Kt, 32 * t + (lane & 31), s2, lane), qf[s2], sc[t]);
         // masks only on the tiles that need them (the causal diagonal, the key tail): wave-uniform
-        const bool masked = k0 + kBK > Sk || (CAUSAL && k0 + kBK - 1 > qw);
+        // (DOC: also the tiles a document of the wave starts inside — ds_l is the largest start)
+        const bool masked = k0 + kBK > Sk || (CAUSAL && k0 + kBK - 1 > qw) || (DOC && k0 < ds_l);
         float mx = kNegInf;
         {  // last visible key of this lane's row, tile-relative (no limit off the boundary)
           const int lim = masked ? (CAUSAL ? min(qrow, Sk - 1) : Sk - 1) - k0 : (1 << 30);
+          // DOC: first visible key likewise. A row whose document starts past this tile is masked
+          // whole before it has a running max, so these entries are -inf, not kNegInf: P =
+          // exp2(-inf - m_run) = 0 exactly whatever (finite) m_run is, where kNegInf · scale - m_run
+          // would be a huge positive exponent while m_run is still kNegInf.
+          const int lo = DOC && masked ? ds - k0 : -(1 << 30);
 #pragma unroll
           for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int i = 0; i < 16; ++i)
+            for (int i = 0; i < 16; ++i) {
               if (32 * t + kappa(g, i & 7) + 16 * (i >> 3) > lim) sc[t][i] = kNegInf;
+              if constexpr (DOC)
+                if (32 * t + kappa(g, i & 7) + 16 * (i >> 3) < lo) sc[t][i] = -__builtin_inff();
+            }
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -329,13 +363,15 @@ __global__ __launch_bounds__(256) void fa_bwd_pre_kernel(const uint16_t* __restr
 
 // dQ: one workgroup = NW waves x 32 query rows of one (batch, q head); S^T and dP^T with the
 // query on the lane (as the forward), dQ^T += K^T · dS^T. NW = 8 pairs two waves per SIMD.
-template <int D, bool CAUSAL, int NW>
+// DOC: the forward's document mask (first tile, wave skip, lower limit) with the same clamping.
+template <int D, bool CAUSAL, int NW, bool DOC = false>
 __global__ __launch_bounds__(64 * NW) void fa_bwd_dq_kernel(
     const uint16_t* __restrict__ Q, const uint16_t* __restrict__ K, const uint16_t* __restrict__ V,
     const uint16_t* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ delta,
     uint16_t* __restrict__ dQ, int Sq, int Sk, int Hq, int Hkv, Strides qs, Strides ks, Strides vs, Strides dos,
-    Strides dqs, float scale_log2, float scale, int nqb) {
+    Strides dqs, float scale_log2, float scale, int nqb, const int* __restrict__ DS) {
   constexpr int KS = D / 16, NT = D / 32, BQ = 32 * NW;
+  static_assert(!DOC || CAUSAL, "the document mask is a refinement of the causal one");
   // [stage][K (row reads for S^T, transposed reads for dQ), V (row reads for dP^T)]
   __shared__ __attribute__((aligned(16))) uint8_t KVs[2][2][kBK * D * 2];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 5;
@@ -367,19 +403,31 @@ __global__ __launch_bounds__(64 * NW) void fa_bwd_dq_kernel(
       for (int i = 0; i < 16; ++i) acc[n][i] = 0.f;
     const int kend = CAUSAL ? min(Sk, q0 + BQ) : Sk;
     const int ntiles = (kend + kBK - 1) / kBK;
-    dma_tile<D, NW>(Kb, ks.s, 0, Sk, KVs[0][0], w, lane);
-    dma_tile<D, NW>(Vb, vs.s, 0, Sk, KVs[0][1], w, lane);
-    for (int j = 0; j < ntiles; ++j) {
+    // DOC: this lane's first visible key, the wave's smallest / largest one, the block's first tile
+    // (all clamped into range; see the forward)
+    int ds = 0, ds_w = 0, ds_l = 0, jbeg = 0;
+    if constexpr (DOC) {
+      const int* DSb = DS + (int64_t)b * Sq;
+      const int r = min(qrow, Sq - 1);
+      ds = min(max(DSb[r], 0), r);
+      ds_w = __builtin_amdgcn_readlane(ds, 0);
+      ds_l = __builtin_amdgcn_readlane(ds, 31);
+      jbeg = min(max(DSb[q0], 0), q0) / kBK;
+    }
+    dma_tile<D, NW>(Kb, ks.s, jbeg * kBK, Sk, KVs[0][0], w, lane);
+    dma_tile<D, NW>(Vb, vs.s, jbeg * kBK, Sk, KVs[0][1], w, lane);
+    for (int j = jbeg; j < ntiles; ++j) {
       const int k0 = j * kBK;
+      const int st = DOC ? j - jbeg : j;  // the stage parity counts from the first tile loaded
       dma_barrier();
       if (j + 1 < ntiles) {
-        dma_tile<D, NW>(Kb, ks.s, k0 + kBK, Sk, KVs[(j + 1) & 1][0], w, lane);
-        dma_tile<D, NW>(Vb, vs.s, k0 + kBK, Sk, KVs[(j + 1) & 1][1], w, lane);
+        dma_tile<D, NW>(Kb, ks.s, k0 + kBK, Sk, KVs[(st + 1) & 1][0], w, lane);
+        dma_tile<D, NW>(Vb, vs.s, k0 + kBK, Sk, KVs[(st + 1) & 1][1], w, lane);
       }
-      const uint8_t* Kt = KVs[j & 1][0];
-      const uint8_t* Vt = KVs[j & 1][1];
-      if (!CAUSAL || k0 <= qw + 31) {
-        const bool masked = k0 + kBK > Sk || (CAUSAL && k0 + kBK - 1 > qw);  // wave-uniform
+      const uint8_t* Kt = KVs[st & 1][0];
+      const uint8_t* Vt = KVs[st & 1][1];
+      if ((!CAUSAL || k0 <= qw + 31) && (!DOC || k0 + kBK - 1 >= ds_w)) {
+        const bool masked = k0 + kBK > Sk || (CAUSAL && k0 + kBK - 1 > qw) || (DOC && k0 < ds_l);  // wave-uniform
         // one 32-key half at a time keeps S^T / dP^T at 32 live registers
 #pragma unroll 1
         for (int t = 0; t < 2; ++t) {
@@ -394,10 +442,13 @@ __global__ __launch_bounds__(64 * NW) void fa_bwd_dq_kernel(
           // dS^T = P^T (dP^T - delta), P^T = exp2(S^T c - lse); the softmax scale of dS folds into the end
           // last visible key of this lane's row, relative to the half tile (no limit off the boundary)
           const int lim = masked ? (CAUSAL ? min(qrow, Sk - 1) : Sk - 1) - k0 - 32 * t : (1 << 30);
+          const int lo = DOC && masked ? ds - k0 - 32 * t : -(1 << 30);  // (DOC) first visible key
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             float p = __builtin_amdgcn_exp2f(fmaf(sc[i], scale_log2, -lse));
             if (kappa(g, i & 7) + 16 * (i >> 3) > lim) p = 0.f;
+            if constexpr (DOC)
+              if (kappa(g, i & 7) + 16 * (i >> 3) < lo) p = 0.f;
             sc[i] = p * (dp[i] - dl);
           }
           bf16x8 sf[2];
@@ -456,14 +507,22 @@ __global__ __launch_bounds__(64 * NW) void fa_bwd_dq_kernel(
 // the batches): Σ dQ from the dQ tiles, Σ dV from the dV^T accumulators after they are stored,
 // Σ dK = 0 exactly (Σ_k dS[q][k] = δ_q - δ_q) — the separate pass re-read all of dQKV (r5: 62.5 us
 // per ViT-L layer against +12 us here).
-template <int D, bool CAUSAL, int KW, bool FQ = false, int NG_ = 8 / KW>
+//
+// DOC (causal, Sq == Sk): key k is seen by queries k .. doc_end[k] - 1 only. Each lane's upper
+// query limit comes from its key's doc_end (clamped to [key + 1, Sq], so a malformed array cannot
+// move a loop bound or a DMA row out of range); doc_end is non-decreasing, so the workgroup's
+// query range ends at the doc_end of its last valid key (fewer items), and a wave skips an item
+// that starts at or past the doc_end of its own last key. LDS stages, DMA pattern and the group
+// reduction are the plain kernel's.
+template <int D, bool CAUSAL, int KW, bool FQ = false, int NG_ = 8 / KW, bool DOC = false>
 __global__ __launch_bounds__(64 * KW * NG_, 8 / (KW * NG_)) void fa_bwd_dkdv_kernel(
     const uint16_t* __restrict__ Q, const uint16_t* __restrict__ K, const uint16_t* __restrict__ V,
     const uint16_t* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ delta,
     uint16_t* __restrict__ dK, uint16_t* __restrict__ dV, int Sq, int Sk, int Hq, int Hkv, Strides qs, Strides ks,
     Strides vs, Strides dos, Strides dks, Strides dvs, float scale_log2, float scale, int nsplit,
     float* __restrict__ wsk, float* __restrict__ wsv, uint16_t* __restrict__ dQo, Strides dqs,
-    float* __restrict__ dbp) {
+    float* __restrict__ dbp, const int* __restrict__ DE) {
+  static_assert(!DOC || (CAUSAL && !FQ), "the document mask is a refinement of the causal one");
   constexpr int NG = NG_, BK = 32 * KW;             // groups; keys per workgroup
   constexpr int KS = D / 16, NT = D / 32, QB = 32;  // query rows per work item
   constexpr int TILE = QB * D * 2;                  // bytes of one Q (or dO) tile
@@ -528,7 +587,17 @@ __global__ __launch_bounds__(64 * KW * NG_, 8 / (KW * NG_)) void fa_bwd_dkdv_ker
 #pragma unroll
     for (int i = 0; i < 16; ++i) adk[n][i] = adv[n][i] = 0.f;
   const int qstart = CAUSAL ? (k0 / QB) * QB : 0;
-  const int nqt = (Sq - qstart + QB - 1) / QB;
+  // DOC: de = one past the last query that sees this lane's key, de_w the wave's last key's,
+  // qend the block's last valid key's (keys past Sk take key Sk - 1's; every value in (key, Sq])
+  int de = Sq, de_w = Sq, qend = Sq;
+  if constexpr (DOC) {
+    const int* DEb = DE + (int64_t)b * Sq;
+    const int r = min(krow, Sq - 1), rb = min(k0 + BK - 1, Sq - 1);
+    de = min(max(DEb[r], r + 1), Sq);
+    de_w = __builtin_amdgcn_readlane(de, 31);
+    qend = min(max(DEb[rb], rb + 1), Sq);
+  }
+  const int nqt = ((DOC ? qend : Sq) - qstart + QB - 1) / QB;
   const int total = hpw * nqt, niter = (total + NG - 1) / NG;
   uint8_t* gsm = smem + VBLK + G * 2 * STAGE;
   auto issue = [&](int it, int st) {  // rows past Sq read row Sq - 1 (masked below)
@@ -588,7 +657,7 @@ __global__ __launch_bounds__(64 * KW * NG_, 8 / (KW * NG_)) void fa_bwd_dkdv_ker
     if constexpr (FQ)
       if (k > 0) dq_tile(it - 1, DSl + ((k - 1) & 1) * DSB);
     const int qt0 = qstart + (it % nqt) * QB;
-    if (it < total && (!CAUSAL || qt0 + QB - 1 >= kw)) {
+    if (it < total && (!CAUSAL || qt0 + QB - 1 >= kw) && (!DOC || qt0 < de_w)) {
       const uint8_t* Qt = gsm + (k & 1) * STAGE;
       const uint8_t* Dt = Qt + TILE;
       const float* lse_s = reinterpret_cast<const float*>(Qt + 2 * TILE);
@@ -602,7 +671,7 @@ __global__ __launch_bounds__(64 * KW * NG_, 8 / (KW * NG_)) void fa_bwd_dkdv_ker
         dp = mfma32(ld_rowfrag<D>(Dt, lane & 31, s, lane), ld_rowfrag<D>(Vblk, 32 * wq + (lane & 31), s, lane), dp);
       }
       // element i: query qt0 + kappa(g, i&7) + 16(i>>3), key krow; visible iff lo <= ql < hi
-      const int lo = krow >= Sk ? (1 << 30) : (CAUSAL ? krow - qt0 : -1), hi = Sq - qt0;
+      const int lo = krow >= Sk ? (1 << 30) : (CAUSAL ? krow - qt0 : -1), hi = (DOC ? de : Sq) - qt0;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int ql = kappa(g, i & 7) + 16 * (i >> 3);
@@ -794,11 +863,24 @@ void check_bshd(const at::Tensor& t, const char* name, int64_t D) {
               "flash_attn: ", name, " needs 16-B aligned rows");
 }
 
+// per-token document bounds (doc_start / doc_end): int32 [B, S] contiguous, on q's device. Their
+// VALUES are not checked (that would be a host sync); the kernels clamp them into range.
+const int* doc_bounds(const c10::optional<at::Tensor>& t, const char* name, const at::Tensor& q, bool causal,
+                      int64_t Sk) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(causal && q.size(1) == Sk, "flash_attn: ", name, " needs causal attention with Sq == Sk");
+  TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 2 && t->size(0) == q.size(0) && t->size(1) == q.size(1) &&
+                  t->is_contiguous() && t->device() == q.device(),
+              "flash_attn: ", name, " must be a contiguous int32 [B, S] tensor on q's device");
+  return t->data_ptr<int>();
+}
+
 }  // namespace
 
-// q [B, Sq, Hq, D], k / v [B, Sk, Hkv, D] -> (o [B, Sq, Hq, D], lse [B, Hq, Sq] fp32, log2 domain)
+// q [B, Sq, Hq, D], k / v [B, Sk, Hkv, D] -> (o [B, Sq, Hq, D], lse [B, Hq, Sq] fp32, log2 domain).
+// doc_start (packed sequences, causal only): key k is visible to query q iff doc_start[b, q] <= k <= q.
 std::vector<at::Tensor> flash_attn_forward(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, bool causal,
-                                           double scale) {
+                                           double scale, const c10::optional<at::Tensor>& doc_start) {
   const int64_t D = q.size(3);
   TORCH_CHECK(D == 64 || D == 128, "flash_attn: head dim 64 or 128");
   check_bshd(q, "q", D);
@@ -808,6 +890,7 @@ std::vector<at::Tensor> flash_attn_forward(const at::Tensor& q, const at::Tensor
   TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == B && Hq % Hkv == 0, "flash_attn: q/k/v shape mismatch");
   TORCH_CHECK(!causal || Sq == Sk, "flash_attn: causal needs Sq == Sk");
   TORCH_CHECK(Sq > 0 && Sk > 0 && B * Hq < 65536 && Sq < (1 << 30), "flash_attn: bad size");
+  const int* ds = doc_bounds(doc_start, "doc_start", q, causal, Sk);
   auto o = at::empty({B, Sq, Hq, D}, q.options());
   auto lse = at::empty({B, Hq, Sq}, q.options().dtype(at::kFloat));
   auto stream = c10::hip::getCurrentHIPStream(q.device().index()).stream();
@@ -821,18 +904,22 @@ std::vector<at::Tensor> flash_attn_forward(const at::Tensor& q, const at::Tensor
     hipLaunchKernelGGL(kern, grid, dim3(64 * nw), 0, stream, reinterpret_cast<const uint16_t*>(q.data_ptr()),
                        reinterpret_cast<const uint16_t*>(k.data_ptr()), reinterpret_cast<const uint16_t*>(v.data_ptr()),
                        reinterpret_cast<uint16_t*>(o.data_ptr()), lse.data_ptr<float>(), (int)Sq, (int)Sk, (int)Hq,
-                       (int)Hkv, strides_of(q), strides_of(k), strides_of(v), strides_of(o), sl2, nqb);
+                       (int)Hkv, strides_of(q), strides_of(k), strides_of(v), strides_of(o), sl2, nqb, ds);
     XDDP_HIP_CHECK(hipGetLastError());
   };
 #define XDDP_FA(D_, C_) \
   if (nw == 8) go(fa_fwd_kernel<D_, C_, 8>); else go(fa_fwd_kernel<D_, C_, 4>)
+#define XDDP_FA_DOC(D_) \
+  if (nw == 8) go(fa_fwd_kernel<D_, true, 8, false, true>); else go(fa_fwd_kernel<D_, true, 4, false, true>)
   // short non-causal D = 64 heads (ViT: 197 keys) stage all of K / V at once (r3 A/B vs the
   // double-buffered tile loop: profiles/r3_flash_whole_kv_ab.txt)
   const bool whole = D == 64 && !causal && Sk <= 4 * kBK;
-  if (D == 128) { if (causal) { XDDP_FA(128, true); } else { XDDP_FA(128, false); } }
+  if (ds) { if (D == 128) { XDDP_FA_DOC(128); } else { XDDP_FA_DOC(64); } }
+  else if (D == 128) { if (causal) { XDDP_FA(128, true); } else { XDDP_FA(128, false); } }
   else if (whole) { if (nw == 8) go(fa_fwd_kernel<64, false, 8, true>); else go(fa_fwd_kernel<64, false, 4, true>); }
   else { if (causal) { XDDP_FA(64, true); } else { XDDP_FA(64, false); } }
 #undef XDDP_FA
+#undef XDDP_FA_DOC
   return {o, lse};
 }
 
@@ -842,7 +929,9 @@ std::vector<at::Tensor> flash_attn_backward(const at::Tensor& dout, const at::Te
                                             bool causal, double scale, const c10::optional<at::Tensor>& dq_out,
                                             const c10::optional<at::Tensor>& dk_out,
                                             const c10::optional<at::Tensor>& dv_out,
-                                            const c10::optional<at::Tensor>& bias_like) {
+                                            const c10::optional<at::Tensor>& bias_like,
+                                            const c10::optional<at::Tensor>& doc_start,
+                                            const c10::optional<at::Tensor>& doc_end) {
   const int64_t D = q.size(3);
   TORCH_CHECK(D == 64 || D == 128, "flash_attn: head dim 64 or 128");
   check_bshd(q, "q", D);
@@ -854,6 +943,10 @@ std::vector<at::Tensor> flash_attn_backward(const at::Tensor& dout, const at::Te
   TORCH_CHECK(dout.sizes() == q.sizes() && o.sizes() == q.sizes() && lse.is_contiguous() &&
                   lse.numel() == B * Hq * Sq && lse.scalar_type() == at::kFloat,
               "flash_attn backward: shape mismatch");
+  // packed sequences: the dQ kernel masks by doc_start (query on the lane), dK/dV by doc_end (key on the lane)
+  const int* ds = doc_bounds(doc_start, "doc_start", q, causal, Sk);
+  const int* de = doc_bounds(doc_end, "doc_end", q, causal, Sk);
+  TORCH_CHECK((ds == nullptr) == (de == nullptr), "flash_attn backward: doc_start and doc_end come together");
   // optional caller-provided outputs (e.g. strided views of one packed [B, S, 3, H, D] gradient, so
   // a fused qkv projection gets its gradient without a gather)
   auto out_or = [&](const c10::optional<at::Tensor>& o_, const at::Tensor& like, int64_t S_, int64_t H_) {
@@ -897,14 +990,18 @@ std::vector<at::Tensor> flash_attn_backward(const at::Tensor& dout, const at::Te
                          reinterpret_cast<const uint16_t*>(dout.data_ptr()), lse.data_ptr<float>(),
                          delta.data_ptr<float>(), reinterpret_cast<uint16_t*>(dq.data_ptr()), (int)Sq, (int)Sk,
                          (int)Hq, (int)Hkv, strides_of(q), strides_of(k), strides_of(v), strides_of(dout),
-                         strides_of(dq), sl2, sc, nqb);
+                         strides_of(dq), sl2, sc, nqb, ds);
       XDDP_HIP_CHECK(hipGetLastError());
     };
 #define XDDP_FA(D_, C_) \
   if (nw == 8) go(fa_bwd_dq_kernel<D_, C_, 8>); else go(fa_bwd_dq_kernel<D_, C_, 4>)
-    if (D == 128) { if (causal) { XDDP_FA(128, true); } else { XDDP_FA(128, false); } }
+#define XDDP_FA_DOC(D_) \
+  if (nw == 8) go(fa_bwd_dq_kernel<D_, true, 8, true>); else go(fa_bwd_dq_kernel<D_, true, 4, true>)
+    if (ds) { if (D == 128) { XDDP_FA_DOC(128); } else { XDDP_FA_DOC(64); } }
+    else if (D == 128) { if (causal) { XDDP_FA(128, true); } else { XDDP_FA(128, false); } }
     else { if (causal) { XDDP_FA(64, true); } else { XDDP_FA(64, false); } }
 #undef XDDP_FA
+#undef XDDP_FA_DOC
   }
   {
     const int nkb = (int)((Sk + 32 * kwv - 1) / (32 * kwv));
@@ -958,10 +1055,13 @@ std::vector<at::Tensor> flash_attn_backward(const at::Tensor& dout, const at::Te
                          strides_of(k), strides_of(v), strides_of(dout), strides_of(dk), strides_of(dv), sl2, sc,
                          nsplit, nsplit > 1 ? wsk.data_ptr<float>() : nullptr,
                          nsplit > 1 ? wsv.data_ptr<float>() : nullptr, reinterpret_cast<uint16_t*>(dq.data_ptr()),
-                         strides_of(dq), dbp.defined() ? dbp.data_ptr<float>() : nullptr);
+                         strides_of(dq), dbp.defined() ? dbp.data_ptr<float>() : nullptr, de);
       XDDP_HIP_CHECK(hipGetLastError());
     };
-    if (D == 128) {
+    if (de) {  // (causal, so kwv == 4)
+      if (D == 128) go(fa_bwd_dkdv_kernel<128, true, 4, false, 1, true>);
+      else go(fa_bwd_dkdv_kernel<64, true, 4, false, 2, true>);
+    } else if (D == 128) {
       if (causal) go(fa_bwd_dkdv_kernel<128, true, 4, false, 1>); else go(fa_bwd_dkdv_kernel<128, false, 4, false, 1>);
     }
     else if (kwv == 8) go(fa_bwd_dkdv_kernel<64, false, 8, true>);

@@ -110,7 +110,8 @@ at::Tensor maxpool_backward(const at::Tensor& dy, const at::Tensor& idx, const a
                             int64_t stride, int64_t pad, const c10::optional<at::Tensor>& dy2);
 
 // transformer elementwise kernels (csrc/kernels/transformer.hip)
-at::Tensor rope(const at::Tensor& x, const at::Tensor& cosv, const at::Tensor& sinv, bool backward);
+at::Tensor rope(const at::Tensor& x, const at::Tensor& cosv, const at::Tensor& sinv, bool backward,
+                const c10::optional<at::Tensor>& positions = c10::nullopt);
 at::Tensor swiglu_forward(const at::Tensor& a, const at::Tensor& b);
 std::vector<at::Tensor> swiglu_backward(const at::Tensor& g, const at::Tensor& a, const at::Tensor& b);
 at::Tensor gelu_forward(const at::Tensor& h);
@@ -120,13 +121,15 @@ std::vector<at::Tensor> bias_grad(const at::Tensor& g, const c10::optional<at::T
 
 // flash attention, [B, S, H, D] bf16 (csrc/kernels/flash_attn.hip)
 std::vector<at::Tensor> flash_attn_forward(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, bool causal,
-                                           double scale);
+                                           double scale, const c10::optional<at::Tensor>& doc_start = c10::nullopt);
 std::vector<at::Tensor> flash_attn_backward(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k,
                                             const at::Tensor& v, const at::Tensor& o, const at::Tensor& lse,
                                             bool causal, double scale, const c10::optional<at::Tensor>& dq_out,
                                             const c10::optional<at::Tensor>& dk_out,
                                             const c10::optional<at::Tensor>& dv_out,
-                                            const c10::optional<at::Tensor>& bias_like);
+                                            const c10::optional<at::Tensor>& bias_like,
+                                            const c10::optional<at::Tensor>& doc_start = c10::nullopt,
+                                            const c10::optional<at::Tensor>& doc_end = c10::nullopt);
 
 void bind_norm_kernels(pybind11::module_& m);
 

@@ -56,11 +56,13 @@ void bind_norm_kernels(py::module_& m) {
         "4 GELU backward (residual = h): {(a @ w.T) * gelu'(h), column sums} | 5 BatchNorm statistics: "
         "{y, partials [3, N, mtiles] group-minor}");
   m.def("flash_attn_forward", &flash_attn_forward, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
-        py::arg("scale"));
+        py::arg("scale"), py::arg("doc_start") = py::none());
   m.def("flash_attn_backward", &flash_attn_backward, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o"), py::arg("lse"), py::arg("causal"), py::arg("scale"), py::arg("dq_out") = py::none(),
-        py::arg("dk_out") = py::none(), py::arg("dv_out") = py::none(), py::arg("bias_like") = py::none());
-  m.def("rope", &rope, py::arg("x"), py::arg("cos"), py::arg("sin"), py::arg("backward") = false);
+        py::arg("dk_out") = py::none(), py::arg("dv_out") = py::none(), py::arg("bias_like") = py::none(),
+        py::arg("doc_start") = py::none(), py::arg("doc_end") = py::none());
+  m.def("rope", &rope, py::arg("x"), py::arg("cos"), py::arg("sin"), py::arg("backward") = false,
+        py::arg("positions") = py::none());
   m.def("swiglu_forward", &swiglu_forward, py::arg("a"), py::arg("b"));
   m.def("swiglu_backward", &swiglu_backward, py::arg("grad"), py::arg("a"), py::arg("b"));
   m.def("stem_conv_forward", &stem_conv_forward, py::arg("x"), py::arg("w"));

@@ -28,15 +28,18 @@ constexpr int kBlock = 256;
 // x, y: [rows = B*S*H, Dh] contiguous (token-major: row r has position s = (r / H) % S).
 // Pair (2i, 2i+1) of a row rotates by angle (s, i): y0 = x0 c - x1 s, y1 = x0 s + x1 c.
 // BWD applies the transpose rotation: dx0 = dy0 c + dy1 s, dx1 = -dy0 s + dy1 c.
-template <typename T, bool BWD>
+// POS (packed sequences): the table row is pos[b, s] (int32 [B, S], clamped to the table's
+// [0, tlen) here: the values are not checked on the host) instead of s.
+template <typename T, bool BWD, bool POS = false>
 __global__ __launch_bounds__(kBlock) void rope_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                       const float* __restrict__ cosv, const float* __restrict__ sinv,
-                                                      int64_t nvec, int H, int S, int Dh) {
+                                                      int64_t nvec, int H, int S, int Dh,
+                                                      const int* __restrict__ pos, int tlen) {
   const int vpr = Dh / 8;  // 16-B vectors per row
   for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
     const int64_t row = v / vpr;
     const int i0 = (int)(v - row * vpr) * 4;  // first rotary pair of this vector
-    const int s = (int)((row / H) % S);
+    const int s = POS ? min(max(pos[row / H], 0), tlen - 1) : (int)((row / H) % S);
     float a[8], c[4], sn[4];
     Vec8<T>::ld(x + v * 8, a);
     const dev::f32x4 cc = *reinterpret_cast<const dev::f32x4*>(cosv + (int64_t)s * (Dh / 2) + i0);
@@ -210,8 +213,10 @@ void check_vec(const at::Tensor& t, const char* what) {
 }  // namespace
 
 // x: [B, S, H, Dh] contiguous; cos/sin: [>= S, Dh/2] fp32 contiguous. Returns the rotated tensor
-// (backward = the inverse rotation, applied to the incoming gradient).
-at::Tensor rope(const at::Tensor& x, const at::Tensor& cosv, const at::Tensor& sinv, bool backward) {
+// (backward = the inverse rotation, applied to the incoming gradient). positions (optional, int32
+// [B, S] contiguous): the table row of each token instead of its index s.
+at::Tensor rope(const at::Tensor& x, const at::Tensor& cosv, const at::Tensor& sinv, bool backward,
+                const c10::optional<at::Tensor>& positions) {
   check_vec(x, "rope");
   TORCH_CHECK(x.dim() == 4, "rope: x must be [B, S, H, Dh]");
   const int S = (int)x.size(1), H = (int)x.size(2), Dh = (int)x.size(3);
@@ -220,16 +225,23 @@ at::Tensor rope(const at::Tensor& x, const at::Tensor& cosv, const at::Tensor& s
                   sinv.is_contiguous() && cosv.dim() == 2 && cosv.size(0) >= S && cosv.size(1) == Dh / 2 &&
                   sinv.sizes() == cosv.sizes() && cosv.is_cuda(),
               "rope: cos/sin must be fp32 [>= S, Dh/2] on the GPU");
+  const bool has_pos = positions.has_value() && positions->defined();
+  if (has_pos)
+    TORCH_CHECK(positions->scalar_type() == at::kInt && positions->dim() == 2 && positions->size(0) == x.size(0) &&
+                    positions->size(1) == S && positions->is_contiguous() && positions->device() == x.device(),
+                "rope: positions must be a contiguous int32 [B, S] tensor on x's device");
   auto y = at::empty_like(x);
   const int64_t nvec = x.numel() / 8;
   if (nvec == 0) return y;
   auto stream = c10::hip::getCurrentHIPStream(x.device().index()).stream();
+  const int* pos = has_pos ? positions->data_ptr<int>() : nullptr;
   dispatch16(x.scalar_type(), [&](auto tag) {
     using T = decltype(tag);
-    auto k = backward ? rope_kernel<T, true> : rope_kernel<T, false>;
+    auto k = has_pos ? (backward ? rope_kernel<T, true, true> : rope_kernel<T, false, true>)
+                     : (backward ? rope_kernel<T, true> : rope_kernel<T, false>);
     hipLaunchKernelGGL(k, dim3(grid_for(nvec)), dim3(kBlock), 0, stream, reinterpret_cast<const T*>(x.data_ptr()),
                        reinterpret_cast<T*>(y.data_ptr()), cosv.data_ptr<float>(), sinv.data_ptr<float>(), nvec, H, S,
-                       Dh);
+                       Dh, pos, (int)cosv.size(0));
     XDDP_HIP_CHECK(hipGetLastError());
   });
   return y;

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.attention import flash_attention
+from ..ops.attention import doc_mask, flash_attention
 from ..ops.layer_norm import FusedRMSNorm
 from ..ops.linear import linear, multi_linear
 from ..ops.transformer import rope, rope_reference, swiglu
@@ -59,11 +59,14 @@ class Attention(nn.Module):
         self.wv = nn.Linear(cfg.dim, self.kvh * self.hd, bias=False)
         self.wo = nn.Linear(self.h * self.hd, cfg.dim, bias=False)
 
-    def forward(self, x, cos, sin, residual=None):
+    def forward(self, x, cos, sin, residual=None, docs=None):
         """Attention output; with ``residual`` (fused path) ``residual + attention`` (the skip
-        connection added in the o-projection GEMM's epilogue)."""
+        connection added in the o-projection GEMM's epilogue). ``docs`` (packed sequences,
+        ``data/packing.py``): positions restart and attention stops at document boundaries."""
         B, S, _ = x.shape
         rot = rope if _fused() else rope_reference
+        if docs is not None:
+            return self._forward_docs(x, cos, sin, residual, docs, rot)
         # rotate in the projection's [B, S, H, Dh] layout, then move heads forward for attention
         if _fused():
             # q / k / v from one input with their input gradient accumulated in GEMMs (ops/linear.py
@@ -85,6 +88,31 @@ class Attention(nn.Module):
             k = k.repeat_interleave(rep, dim=1)
             v = v.repeat_interleave(rep, dim=1)
         o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+        out = self.wo(o.transpose(1, 2).reshape(B, S, -1))
+        return out if residual is None else residual + out
+
+    def _forward_docs(self, x, cos, sin, residual, docs, rot):
+        """``forward`` on a packed batch: rotary tables indexed by ``docs.positions`` and the
+        document-masked attention (the gfx950 kernels on the fused path, their SDPA fallback with
+        the equivalent boolean mask on the reference path)."""
+        B, S, _ = x.shape
+        pos = docs.positions
+        if _fused():
+            q, k, v = multi_linear(x, self.wq.weight, self.wk.weight, self.wv.weight)
+        else:
+            q, k, v = self.wq(x), self.wk(x), self.wv(x)
+        q = rot(q.view(B, S, self.h, self.hd), cos, sin, pos)
+        k = rot(k.view(B, S, self.kvh, self.hd), cos, sin, pos)
+        v = v.view(B, S, self.kvh, self.hd)
+        if _fused():
+            o = flash_attention(q, k, v, causal=True, docs=docs)
+            return linear(o.reshape(B, S, -1), self.wo.weight, residual)
+        q, k, v = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)
+        if self.kvh != self.h:
+            rep = self.h // self.kvh
+            k = k.repeat_interleave(rep, dim=1)
+            v = v.repeat_interleave(rep, dim=1)
+        o = F.scaled_dot_product_attention(q, k, v, attn_mask=doc_mask(docs.doc_start.to(x.device), True))
         out = self.wo(o.transpose(1, 2).reshape(B, S, -1))
         return out if residual is None else residual + out
 
@@ -111,15 +139,15 @@ class Block(nn.Module):
         self.ffn_norm = FusedRMSNorm(cfg.dim, eps=cfg.norm_eps)
         self.feed_forward = FeedForward(cfg)
 
-    def forward(self, x, cos, sin):
+    def forward(self, x, cos, sin, docs=None):
         if _fused() and os.environ.get("XDDP_NORM_SKIP", "1") != "0":
             # each norm's input is also the skip connection: its gradient is summed in the norm's
             # backward kernel (ops/layer_norm.py rms_norm_with_skip), not by an add pass
             y, skip = self.attention_norm.forward_with_skip(x)
-            x = self.attention(y, cos, sin, residual=skip)
+            x = self.attention(y, cos, sin, residual=skip, docs=docs)
             y, skip = self.ffn_norm.forward_with_skip(x)
             return self.feed_forward(y, residual=skip)
-        x = self.attention(self.attention_norm(x), cos, sin, residual=x)
+        x = self.attention(self.attention_norm(x), cos, sin, residual=x, docs=docs)
         return self.feed_forward(self.ffn_norm(x), residual=x)
 
 
@@ -147,14 +175,18 @@ class Llama(nn.Module):
             self._rope[key] = (cos.contiguous(), sin.contiguous())
         return self._rope[key]
 
-    def forward(self, tokens):
+    def forward(self, tokens, docs=None):
+        """Logits ``[B, S, vocab]``. ``docs`` (a ``data.PackedDocs`` of the batch): every document of
+        a packed row is attended and position-encoded as if it were alone in its own sequence."""
         cos, sin = self._tables(tokens.device)
         h = self.tok_embeddings(tokens)
+        if docs is not None:
+            docs = docs.to(tokens.device)
         for blk in self.layers:
             if self.cfg.checkpoint_activations and self.training:
-                h = torch.utils.checkpoint.checkpoint(blk, h, cos, sin, use_reentrant=False)
+                h = torch.utils.checkpoint.checkpoint(blk, h, cos, sin, docs, use_reentrant=False)
             else:
-                h = blk(h, cos, sin)
+                h = blk(h, cos, sin, docs)
         return linear(self.norm(h), self.output.weight) if _fused() else self.output(self.norm(h))
 
 

@@ -16,24 +16,34 @@ from .._native import load
 __all__ = ["rope", "swiglu", "rope_reference"]
 
 
-def rope_reference(x, cos, sin):
-    """PyTorch reference: rotate (even, odd) pairs of the last dim of ``x: [B, S, H, Dh]``."""
+def rope_reference(x, cos, sin, positions=None):
+    """PyTorch reference: rotate (even, odd) pairs of the last dim of ``x: [B, S, H, Dh]``; with
+    ``positions: [B, S]`` (packed sequences) token ``(b, s)`` takes table row ``positions[b, s]``."""
     S = x.shape[1]
-    c, s = cos[:S][None, :, None, :], sin[:S][None, :, None, :]
+    if positions is None:
+        c, s = cos[:S][None, :, None, :], sin[:S][None, :, None, :]
+    else:
+        p = positions.to(device=cos.device, dtype=torch.long)
+        c, s = cos[p][:, :, None, :], sin[p][:, :, None, :]
     x1, x2 = x[..., 0::2].float(), x[..., 1::2].float()
     return torch.stack([x1 * c - x2 * s, x1 * s + x2 * c], dim=-1).flatten(-2).to(x.dtype)
 
 
 class _Rope(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, cos, sin):
+    def forward(ctx, x, cos, sin, positions=None):
         ctx.save_for_backward(cos, sin)
-        return load().rope(x, cos, sin, False)
+        ctx.positions = positions  # int32, not differentiable
+        if positions is None:
+            return load().rope(x, cos, sin, False)
+        return load().rope(x, cos, sin, False, positions)
 
     @staticmethod
     def backward(ctx, dy):
         cos, sin = ctx.saved_tensors
-        return load().rope(dy.contiguous(), cos, sin, True), None, None
+        if ctx.positions is None:
+            return load().rope(dy.contiguous(), cos, sin, True), None, None, None
+        return load().rope(dy.contiguous(), cos, sin, True, ctx.positions), None, None, None
 
 
 class _SwiGLU(torch.autograd.Function):
@@ -54,12 +64,16 @@ def _vec_ok(*ts):
                t.dtype in (torch.bfloat16, torch.float16, torch.float32) for t in ts)
 
 
-def rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
-    """Rotary embedding of ``x: [B, S, H, Dh]`` with fp32 tables ``cos, sin: [>= S, Dh/2]``."""
+def rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+         positions: torch.Tensor | None = None) -> torch.Tensor:
+    """Rotary embedding of ``x: [B, S, H, Dh]`` with fp32 tables ``cos, sin: [>= S, Dh/2]``; with
+    ``positions`` (int32 ``[B, S]``, packed sequences) the table row is ``positions[b, s]``, not ``s``."""
     if (_vec_ok(x) and x.dim() == 4 and x.shape[-1] % 8 == 0 and cos.is_cuda and cos.dtype == torch.float32
             and cos.is_contiguous() and sin.is_contiguous()):
-        return _Rope.apply(x, cos, sin)
-    return rope_reference(x, cos, sin)
+        if positions is None:
+            return _Rope.apply(x, cos, sin)
+        return _Rope.apply(x, cos, sin, positions.to(device=x.device, dtype=torch.int32).contiguous())
+    return rope_reference(x, cos, sin, positions)
 
 
 def swiglu(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

@@ -4,6 +4,7 @@
 #include <ATen/ATen.h>
 #include <pybind11/pybind11.h>
 
+#include <tuple>
 #include <vector>
 
 namespace xddp {
@@ -54,6 +55,16 @@ at::Tensor bn_backward_elem(const at::Tensor& g, const at::Tensor& x, const at::
 std::vector<at::Tensor> gemm_nt(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
                                 int64_t epi, const c10::optional<at::Tensor>& residual,
                                 const c10::optional<at::Tensor>& out);
+// FP8 linear layers (fp8_cast.hip, gemm_fp8.hip); fmt 0 = e4m3, 1 = e5m2 (OCP), bytes in uint8 tensors.
+// fp8_amax: max |x| of a bf16 tensor -> float32[1]. fp8_quantize: x [R, C] bf16 -> {q [R, C], qT [C, R] if
+// transpose, scale float32[1] = FMAX / amax}. gemm_fp8_nt: bf16 y [M, N] = (a · bᵀ) / (scale_a · scale_b),
+// epi 1 adds the residual (which may be out).
+at::Tensor fp8_amax(const at::Tensor& x);
+std::tuple<at::Tensor, c10::optional<at::Tensor>, at::Tensor> fp8_quantize(const at::Tensor& x, const at::Tensor& amax,
+                                                                           int64_t fmt, bool transpose);
+at::Tensor gemm_fp8_nt(const at::Tensor& a, const at::Tensor& b, const at::Tensor& scale_a, const at::Tensor& scale_b,
+                       int64_t a_fmt, int64_t b_fmt, int64_t epi, const c10::optional<at::Tensor>& residual,
+                       const c10::optional<at::Tensor>& out);
 std::vector<at::Tensor> conv3x3_forward(const at::Tensor& x, const at::Tensor& w, int64_t stride, bool stats);
 // the same on the dense GEMM pipeline (gemm.hip; N % 128 == 0, input < 2^31 elements); zeros: a
 // 256-B zero line on the device

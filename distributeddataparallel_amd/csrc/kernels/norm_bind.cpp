@@ -55,6 +55,14 @@ void bind_norm_kernels(py::module_& m) {
         "y = a @ w.T (bf16, MFMA LDS-DMA GEMM) with epilogue 0 none | 1 +bias | 2 +bias->GELU | 3 +residual | "
         "4 GELU backward (residual = h): {(a @ w.T) * gelu'(h), column sums} | 5 BatchNorm statistics: "
         "{y, partials [3, N, mtiles] group-minor}");
+  m.def("fp8_amax", &fp8_amax, py::arg("x"), "max |x| of a bf16 tensor -> float32[1] (device, no host sync)");
+  m.def("fp8_quantize", &fp8_quantize, py::arg("x"), py::arg("amax"), py::arg("fmt"), py::arg("transpose"),
+        "x [R, C] bf16 -> (q [R, C] uint8, qT [C, R] uint8 or None, scale float32[1]); fmt 0 e4m3 | 1 e5m2 (OCP), "
+        "q = fp8(clamp(x * scale, +-FMAX)), scale = FMAX / amax (1 for amax = 0)");
+  m.def("gemm_fp8_nt", &gemm_fp8_nt, py::arg("a"), py::arg("b"), py::arg("scale_a"), py::arg("scale_b"),
+        py::arg("a_fmt"), py::arg("b_fmt"), py::arg("epi") = 0, py::arg("res") = py::none(), py::arg("out") = py::none(),
+        "bf16 y = (a @ b.T) / (scale_a * scale_b) on FP8 bytes (block-scaled MFMA, unit block scales); epi 1: + res "
+        "(res may be out)");
   m.def("flash_attn_forward", &flash_attn_forward, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
         py::arg("scale"), py::arg("doc_start") = py::none());
   m.def("flash_attn_backward", &flash_attn_backward, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),

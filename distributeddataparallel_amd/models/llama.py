@@ -187,7 +187,8 @@ class Llama(nn.Module):
                 h = torch.utils.checkpoint.checkpoint(blk, h, cos, sin, docs, use_reentrant=False)
             else:
                 h = blk(h, cos, sin, docs)
-        return linear(self.norm(h), self.output.weight) if _fused() else self.output(self.norm(h))
+        # (the vocabulary projection stays bf16 under XDDP_FP8, as is standard for FP8 training)
+        return linear(self.norm(h), self.output.weight, fp8=False) if _fused() else self.output(self.norm(h))
 
 
 def llama3_8b(**kw):

@@ -12,6 +12,11 @@ hipBLASLt cannot do (the ViT MLP's dGELU + bias gradient), ``0`` nowhere. On one
 kernel reaches 0.80-0.93x hipBLASLt's plain-GEMM speed on the transformer shapes
 (``profiles/r3_gemm_nt_vs_hipblaslt.txt``), so forward projections stay on hipBLASLt, whose
 beta = 1 residual accumulate is free, unless asked for.
+
+``XDDP_FP8`` (opt-in, ``ops/fp8.py``): ``1`` runs all three GEMMs of every supported projection on
+FP8 operands (own casts and GEMM kernels), ``emulate`` the same recipe in plain torch (CPU too);
+unset or ``0`` leaves every path above as it is. Calls the FP8 path does not support (operands not
+bf16, autocast, a weight dimension or the token count not a multiple of 128) take today's path.
 """
 from __future__ import annotations
 
@@ -24,7 +29,8 @@ import torch.nn.functional as F
 
 from .._native import load
 
-__all__ = ["linear", "multi_linear", "own_gemm_ok", "own_gemm_mode", "set_grad_targets", "clear_grad_targets"]
+__all__ = ["linear", "multi_linear", "own_gemm_ok", "own_gemm_mode", "fp8_mode", "set_grad_targets",
+           "clear_grad_targets"]
 
 # weight -> the tensor its gradient should be written into (DDP with gradient_as_bucket_view
 # registers each parameter's view of its bucket, ``DistributedDataParallel._pre_forward``)
@@ -56,12 +62,45 @@ def set_grad_targets(params, targets) -> None:
 def _dw(dy2: torch.Tensor, x2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """``dW = dY2ᵀ·X2`` for weight ``w`` — into its registered target when ``w`` has no gradient
     yet (the first contribution of this backward), returned as a fresh alias of it."""
-    e = _GRAD_TARGETS.pop(id(w), None)  # one claim per registration: a weight used twice in a
-    t = e[1]() if e is not None and e[0]() is w else None  # forward gets one target write
-    if t is not None and w.grad is None and not torch.is_grad_enabled():
+    t = _claim_grad_target(w)
+    if t is not None:
         torch.mm(dy2.t(), x2, out=t)
         return t.view(t.shape)
     return torch.mm(dy2.t(), x2)
+
+
+def _claim_grad_target(w: torch.Tensor) -> Optional[torch.Tensor]:
+    """The registered gradient target of ``w`` if this backward may write its ``dW`` there (``w``
+    holds no gradient yet), else None; either way the registration is used up."""
+    e = _GRAD_TARGETS.pop(id(w), None)  # one claim per registration: a weight used twice in a
+    t = e[1]() if e is not None and e[0]() is w else None  # forward gets one target write
+    return t if t is not None and w.grad is None and not torch.is_grad_enabled() else None
+
+
+def fp8_mode() -> str:
+    """``XDDP_FP8``: ``"1"`` (FP8 kernels), ``"emulate"`` (the same recipe in torch) or ``"0"`` (default)."""
+    v = os.environ.get("XDDP_FP8", "0")
+    return v if v in ("1", "emulate") else "0"
+
+
+def _fp8_route(fp8: Optional[bool], x: torch.Tensor, weights, residual=None) -> str:
+    """The FP8 mode this call runs in (``"0"``: not at all). ``fp8`` None follows the
+    environment, False keeps the call off the FP8 path, True asks for it (the kernels unless the
+    environment says ``emulate``)."""
+    mode = fp8_mode()
+    if fp8 is False or (fp8 is None and mode == "0"):
+        return "0"
+    if mode == "0":
+        mode = "1"
+    if _autocast_on(x):
+        return "0"
+    from . import fp8 as _fp8
+    if not all(_fp8.eligible(mode, x, w) for w in weights):
+        return "0"
+    if residual is not None and (residual.shape != (*x.shape[:-1], weights[0].shape[0])
+                                 or residual.dtype != torch.bfloat16 or residual.device != x.device):
+        return "0"
+    return mode
 
 
 def own_gemm_mode() -> str:
@@ -114,10 +153,16 @@ class _Linear(torch.autograd.Function):
         return dx, dw, dres
 
 
-def linear(x: torch.Tensor, weight: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+def linear(x: torch.Tensor, weight: torch.Tensor, residual: Optional[torch.Tensor] = None,
+           fp8: Optional[bool] = None) -> torch.Tensor:
     """``x·Wᵀ`` (+ ``residual``) — the own GEMM when the shapes allow it, else the library GEMM,
     with the residual as its beta = 1 accumulate operand (``addmm``: one GEMM, one rounding, no
-    separate add pass over the residual stream)."""
+    separate add pass over the residual stream). ``fp8``: None follows ``XDDP_FP8``, False keeps
+    this call in bf16 whatever the environment says (the LM head), True asks for the FP8 path."""
+    mode = _fp8_route(fp8, x, (weight,), residual)
+    if mode != "0":
+        from . import fp8 as _fp8
+        return _fp8.fp8_linear(mode, x, weight, residual)
     if own_gemm_ok(x, weight) and (residual is None or (residual.shape[:-1] == x.shape[:-1]
                                                         and residual.dtype == torch.bfloat16
                                                         and residual.is_contiguous())):
@@ -186,11 +231,16 @@ class _MultiLinear(torch.autograd.Function):
         return (dx, *dws)
 
 
-def multi_linear(x: torch.Tensor, *weights: torch.Tensor):
+def multi_linear(x: torch.Tensor, *weights: torch.Tensor, fp8: Optional[bool] = None):
     """``x·W_iᵀ`` for each weight (bias-free), the input gradient accumulated in GEMMs (see
     :class:`_MultiLinear`); the own GEMM's path (``XDDP_OWN_GEMM=1``) keeps one :func:`linear` per
-    weight. ``XDDP_MULTI_LINEAR=0``: plain per-weight linears (A/B switch)."""
+    weight. ``XDDP_MULTI_LINEAR=0``: plain per-weight linears (A/B switch). ``fp8`` as in
+    :func:`linear`: on the FP8 path the input is quantized once for all weights."""
+    mode = _fp8_route(fp8, x, weights) if weights else "0"
+    if mode != "0":
+        from . import fp8 as _fp8
+        return _fp8.fp8_multi_linear(mode, x, *weights)
     if os.environ.get("XDDP_MULTI_LINEAR", "1") == "0" or _autocast_on(x) or any(own_gemm_ok(x, w) for w in weights) \
             or not all(w.dtype == x.dtype and w.dim() == 2 for w in weights):
-        return tuple(linear(x, w) for w in weights)
+        return tuple(linear(x, w, fp8=False) for w in weights)
     return _MultiLinear.apply(x, *weights)

@@ -24,6 +24,8 @@ struct f16_t {
 };
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
+// one half of a packed bf16 pair, already isolated in the low 16 bits (v & 0xffff, v >> 16)
+__device__ __forceinline__ float bf(uint32_t bits16) { return __uint_as_float(bits16 << 16); }
 __device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
   f32x2 v = {a, b};
   bf16x2 r = __builtin_convertvector(v, bf16x2);  // v_cvt_pk_bf16_f32 (RNE) on gfx950

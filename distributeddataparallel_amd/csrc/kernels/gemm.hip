@@ -20,13 +20,16 @@
 // 16-B row chunks, where the epilogue math runs. Block ids are remapped XCD-contiguously and
 // each XCD's concurrent tiles form a GM x (32 / GM) block that shares A and B panels in its L2.
 // Rows past M re-read row M - 1 and are not stored.
+//
+// The pipeline (tile geometry and order, DMA layout, K loop, C tile stage, tile-width choice) is
+// gemm_pipeline.h, shared with gemm_fp8.hip; this file holds the bf16 operand traits, the three
+// MODEs' source addressing, the six epilogues and the host entry points.
 #include <c10/hip/HIPStream.h>
 #include <torch/extension.h>
 
-#include <type_traits>
-
 #include "common.h"
 #include "kernels/dev_utils.h"
+#include "kernels/gemm_pipeline.h"
 #include "kernels/norm.h"
 
 namespace xddp {
@@ -35,11 +38,25 @@ namespace kernels {
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-using dev::f32x4;
-using dev::u32x4;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-constexpr int kBM = 256, kBK = 64, kWM = 2, kWN = 4, NW = kWM * kWN, kThreads = 64 * NW;
+constexpr int kBK = 64;  // elements per K-tile: the pipeline's 128-B LDS row
+
+// Operand traits of the shared K loop (gemm_pipeline.h): a fragment is the eight bf16 of one 16-B
+// chunk, two k-halves per K-tile, so a pair costs two mfma_f32_16x16x32_bf16.
+struct Bf16Ops {
+  using Frag = bf16x8;
+  static constexpr int kSteps = 2;
+  template <int H>
+  static __device__ __forceinline__ void pack(Frag (&f)[2][H], const u32x4 (&c)[2][H]) {
+#pragma unroll
+    for (int kh = 0; kh < 2; ++kh)
+#pragma unroll
+      for (int i = 0; i < H; ++i) f[kh][i] = __builtin_bit_cast(bf16x8, c[kh][i]);
+  }
+  static __device__ __forceinline__ f32x4 mfma(bf16x8 b, bf16x8 a, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, c, 0, 0, 0);
+  }
+};
 
 enum Epi : int { kEpiNone = 0, kEpiBias = 1, kEpiBiasGelu = 2, kEpiResidual = 3, kEpiDGelu = 4, kEpiStats = 5 };
 
@@ -69,9 +86,6 @@ struct ConvGeo {
 
 constexpr int kModeDense = 0, kModeConv = 1, kModeDgS2 = 2;
 
-
-__device__ __forceinline__ float bf(uint32_t bits16) { return __uint_as_float(bits16 << 16); }
-
 template <int BN, int EPI, int MODE = kModeDense>
 __global__ __launch_bounds__(kThreads, 1) void gemm_nt_kernel(const uint16_t* __restrict__ A,
                                                               const uint16_t* __restrict__ B,
@@ -80,39 +94,27 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt_kernel(const uint16_t* __
                                                               const uint16_t* res, float* __restrict__ part,
                                                               int M, int N, int K, int ntiles, int64_t ldr,
                                                               ConvGeo cg) {
-  constexpr int AI = kBM / 8 / NW, BI = BN / 8 / NW;  // DMA wave-instructions per stage (8 rows each)
-  static_assert(AI * NW * 8 == kBM && BI * NW * 8 == BN, "tile rows must split evenly over the waves");
-  constexpr int WTM = kBM / kWM, WTN = BN / kWN, TM = WTM / 16, TN = WTN / 16;
-  constexpr int STAGE = (kBM + BN) * 128;
+  using Geo = TileGeo<BN>;
+  constexpr int AI = Geo::AI, BI = Geo::BI, STAGE = Geo::STAGE;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
   constexpr bool CONV = MODE != kModeDense;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wm = wid / kWN, wn = wid % kWN;
-  // Tile order: the XCD remap gives each XCD a contiguous run of logical tiles (32 at a time on
-  // its 32 CUs); logical tiles go through groups of GM m-tiles, M fastest inside a group, so such
-  // a run is a GM x (32 / GM) block of tiles that shares GM A panels and 32 / GM B panels in that
-  // XCD's L2 — instead of one A panel and 32 B panels (a full row of N tiles), which made every
-  // XCD stream all of B (2.6x hipBLASLt's HBM bytes on 8192^3, profiles/r3_pmc_kernels.txt).
-  constexpr int GM = BN == 256 ? 8 : 4;  // 8 x 4 tiles of 256 x 256, 4 x 8 of 256 x 128
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   // DGS2: phase-major blocks (heaviest first), each phase a full M x N tile grid
   const int tiles = MODE == kModeDgS2 ? gridDim.x / 4 : gridDim.x;
   const int pidx = MODE == kModeDgS2 ? blockIdx.x / tiles : 0;
   const int ph = pidx == 0 || pidx == 2, pw = pidx <= 1;  // phase order (1,1) (0,1) (1,0) (0,0)
-  const int wg = dev::xcd_remap(blockIdx.x - pidx * tiles, tiles);
-  const int mtiles = tiles / ntiles, grp = wg / (GM * ntiles), first_m = grp * GM;
-  const int gm = min(mtiles - first_m, GM), local = wg - grp * GM * ntiles;
-  const int mt = first_m + local % gm, nt = local / gm;
-  const int n0 = nt * BN, m0 = mt * kBM;
-  const int pos = lane & 7;  // 16-B slot this lane fills in its 128-B LDS row
+  const TileOrigin org = tile_origin<BN>(blockIdx.x - pidx * tiles, tiles, ntiles);
+  const int mt = org.mt, n0 = org.nt * BN, m0 = mt * kBM;
   // DGS2: the phase's tap count (1 << (ph + pw)) times the Cout blocks; ldb = 9 Cout
   const int nk = MODE == kModeDgS2 ? ((cg.C / kBK) << (ph + pw)) : K / kBK;
   const int ldb = MODE == kModeDgS2 ? 9 * cg.C : K;
 
-  // DMA sources: lane l of wave w fills 16-B slot (l & 7) of rows (w*AI + i)*8 + (l >> 3); the
-  // offsets are recomputed per issue from two per-lane values (few live VGPRs: the 4-phase loop
-  // needs ~224 for accumulators and fragments). Rows past M re-read row M - 1 (never stored).
-  const int drow = wid * 8 + (lane >> 3);                    // + i * 8 NW (A, i < AI) / j * 8 NW (B)
-  const int dchunk = 8 * (pos ^ ((drow >> 1) & 7));          // (row >> 1) & 7 is the same for row + 64 i
+  // DMA sources (layout: gemm_pipeline.h): the offsets are recomputed per issue from two per-lane
+  // values (few live VGPRs: the 4-phase loop needs ~224 for accumulators and fragments). Rows past
+  // M re-read row M - 1 (never stored).
+  const int drow = dma_row(lane, wid);                 // + i * 8 NW (A, i < AI) / j * 8 NW (B)
+  const int dchunk = 8 * dma_src_chunk(lane, drow);  // in elements
   // CONV: per A row, the top-left input pixel of its 3x3 window (packed (ih0 + 2) << 16 | (iw0 + 2))
   // and that pixel's element offset (may point before the row for padding windows; never
   // dereferenced then). Host-checked: the input has < 2^31 elements.
@@ -187,160 +189,31 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt_kernel(const uint16_t* __
     }
   };
 
-  f32x4 acc[TM][TN];
+  f32x4 acc[Geo::TM][Geo::TN];
 #pragma unroll
-  for (int i = 0; i < TM; ++i)
+  for (int i = 0; i < Geo::TM; ++i)
 #pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < Geo::TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  {
-    // 4-phase: each K-tile is 4 phases, one per quadrant (A half x B half) of the wave's output,
-    // 16 MFMAs each; the fragments of the next phase are read while the current phase's MFMAs
-    // run, so the MFMA pipe never waits on LDS. The phase order alternates between even and odd
-    // K-tiles so the last phase of a tile and the first of the next use different fragment
-    // registers: even (A0,B0) (A0,B1) (A1,B1) (A1,B0), odd (A0,B1) (A0,B0) (A1,B0) (A1,B1).
-    // One barrier per K-tile, between phases 1 and 2: by then this wave's reads of the tile's
-    // stage are done (lgkmcnt(0)) and its DMA of tile t+1 (issued after the previous tile's
-    // barrier, four phases ago) has landed (vmcnt(0) - nothing else is in flight); after it the
-    // DMA of tile t+2 goes into this tile's stage and phases 2-3 read the first fragments of t+1.
-    constexpr int HA = TM / 2, HB = TN / 2;
-    static_assert(HB >= 1, "B halves need at least one 16-column fragment");
-    bf16x8 fa0[2][HA], fa1[2][HA], fb0[2][HB], fb1[2][HB];  // [k-half][fragment]
-    // fragment rows of a wave are row0 + 16 i: the XOR term ((row >> 1) & 7) is the same for all
-    // of them, so each k-half needs ONE per-lane byte offset; the rest is an immediate
-    const int ra = wm * WTM + (lane & 15), rb = wn * WTN + (lane & 15);
-    uint32_t a_lds[2], b_lds[2];
-#pragma unroll
-    for (int kh = 0; kh < 2; ++kh) {
-      a_lds[kh] = ra * 128 + 16 * ((kh * 4 + (lane >> 4)) ^ ((ra >> 1) & 7));
-      b_lds[kh] = kBM * 128 + rb * 128 + 16 * ((kh * 4 + (lane >> 4)) ^ ((rb >> 1) & 7));
-    }
-    auto ldA = [&](bf16x8 (&f)[2][HA], int half, int buf) {
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-        for (int i = 0; i < HA; ++i)
-          f[kh][i] = *reinterpret_cast<const bf16x8*>(smem + buf * STAGE + a_lds[kh] + (half * HA + i) * 16 * 128);
-    };
-    auto ldB = [&](bf16x8 (&f)[2][HB], int half, int buf) {
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-        for (int j = 0; j < HB; ++j)
-          f[kh][j] = *reinterpret_cast<const bf16x8*>(smem + buf * STAGE + b_lds[kh] + (half * HB + j) * 16 * 128);
-    };
-    auto mma = [&](const bf16x8 (&a)[2][HA], auto ah, const bf16x8 (&b)[2][HB], auto bh) {
-      constexpr int AH = decltype(ah)::value, BHV = decltype(bh)::value;
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh)
-#pragma unroll
-        for (int i = 0; i < HA; ++i)
-#pragma unroll
-          for (int j = 0; j < HB; ++j)
-            acc[AH * HA + i][BHV * HB + j] =
-                __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[kh][j], a[kh][i], acc[AH * HA + i][BHV * HB + j], 0, 0, 0);
-    };
-    // One phase = the fragment reads for the NEXT phase interleaved into this phase's MFMAs,
-    // MFMA first: the wait the compiler puts before the first MFMA then covers only the reads of
-    // the previous phase (whose MFMAs hid them), never the ones just issued. sched_barrier(0)
-    // keeps every instruction inside its phase.
-    auto interleave = [&](auto nld) {
-      constexpr int NLD = decltype(nld)::value, NM = 2 * HA * HB;
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);       // one MFMA (waits for this phase's fragments)
-      __builtin_amdgcn_sched_group_barrier(0x100, NLD, 0);     // the next phase's reads
-      __builtin_amdgcn_sched_group_barrier(0x008, NM - 1, 0);  // the rest of the MFMAs
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    using LA = std::integral_constant<int, 2 * HA>;  // reads of an A half (both k-halves)
-    using LB = std::integral_constant<int, 2 * HB>;
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    // The loop runs tile PAIRS and is branch-free: a wait counter cannot be tracked through a
-    // conditional load (the compiler then waits for everything), so the last tiles re-read a
-    // valid stage and re-stage the last K-tile instead of skipping; those values are never used.
-    // An odd tile count gets a zero tile in front (virtual tile 0 = zeros written to stage 0, real
-    // tile k = virtual k + 1): its MFMAs add exact zeros, and no tail code raises the register
-    // pressure of the loop.
-    const int odd = nk & 1, nv = nk + odd;
-    auto sync = [&](int t) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      issue(min(t + 2, nv - 1) - odd, t & 1);
-    };
-    if (odd) {
-      for (int q = tid; q < STAGE / 16; q += kThreads) reinterpret_cast<u32x4*>(smem)[q] = u32x4{0u, 0u, 0u, 0u};
-    } else {
-      issue(0, 0);
-    }
-    issue(1 - odd, 1);  // virtual tile 1: real tile 1 (even count) / 0 (odd count)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(AI + BI) : "memory");  // stage 0 ready, stage 1 in flight
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    ldA(fa0, 0, 0);
-    ldB(fb0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    for (int t = 0; t < nv; t += 2) {
-      // even tile t (stage 0): enters with A0, B0 of t
-      ldB(fb1, 1, 0);
-      mma(fa0, I0{}, fb0, I0{});
-      interleave(LB{});
-      ldA(fa1, 1, 0);
-      mma(fa0, I0{}, fb1, I1{});
-      interleave(LA{});
-      sync(t);
-      __builtin_amdgcn_sched_barrier(0);
-      ldA(fa0, 0, 1);  // A0 of t + 1
-      mma(fa1, I1{}, fb1, I1{});
-      interleave(LA{});
-      ldB(fb1, 1, 1);  // B1 of t + 1
-      mma(fa1, I1{}, fb0, I0{});
-      interleave(LB{});
-      // odd tile t + 1 (stage 1): enters with A0, B1 of t + 1
-      ldB(fb0, 0, 1);
-      mma(fa0, I0{}, fb1, I1{});
-      interleave(LB{});
-      ldA(fa1, 1, 1);
-      mma(fa0, I0{}, fb0, I0{});
-      interleave(LA{});
-      sync(t + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      ldA(fa0, 0, 0);  // A0 of t + 2
-      mma(fa1, I1{}, fb0, I0{});
-      interleave(LA{});
-      ldB(fb0, 0, 0);  // B0 of t + 2
-      mma(fa1, I1{}, fb1, I1{});
-      interleave(LB{});
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing re-stage DMAs land before the C tile reuses LDS
-  }
+  k_loop_4phase<BN, Bf16Ops>(tid, nk, acc, issue);
 
-  // ---- epilogue: fp32 -> bf16 C tile through LDS (rows padded 16 B), 16-B row chunks out ----
+  // ---- epilogue: fp32 -> bf16 C tile through LDS, 16-B row chunks out ----
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // every wave is done reading the stages
-  constexpr int CST = BN * 2 + 16;
+  constexpr int CST = Geo::CST;
   uint8_t* Cs = smem;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int row = wm * WTM + i * 16 + (lane & 15);
-      const int col = wn * WTN + j * 16 + (lane >> 4) * 4;
-      f32x4 v = acc[i][j];
-      if (EPI == kEpiBias || EPI == kEpiBiasGelu) {  // bias in fp32 before the one rounding
-        const uint2 bb = *reinterpret_cast<const uint2*>(bias + n0 + col);
-        v[0] += bf(bb.x & 0xffffu);
-        v[1] += bf(bb.x >> 16);
-        v[2] += bf(bb.y & 0xffffu);
-        v[3] += bf(bb.y >> 16);
-      }
-      uint2 pk;
-      pk.x = dev::pack_bf16x2(v[0], v[1]);
-      pk.y = dev::pack_bf16x2(v[2], v[3]);
-      *reinterpret_cast<uint2*>(Cs + row * CST + col * 2) = pk;
+  c_tile_to_lds<BN>(Cs, tid, acc, [&](f32x4 v, int col) {
+    if (EPI == kEpiBias || EPI == kEpiBiasGelu) {  // bias in fp32 before the one rounding
+      const uint2 bb = *reinterpret_cast<const uint2*>(bias + n0 + col);
+      v[0] += bf(bb.x & 0xffffu);
+      v[1] += bf(bb.x >> 16);
+      v[2] += bf(bb.y & 0xffffu);
+      v[3] += bf(bb.y >> 16);
     }
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    return v;
+  });
 
   constexpr int CPR = BN / 8;
-  static_assert(kThreads % CPR == 0, "readout mapping needs a fixed chunk column per thread");
-  const int cc = tid % CPR;
+  const int cc = readout_col<BN>(tid);  // this thread's 16-B chunk column of the C tile
   const int rows_valid = min(kBM, M - m0);
   u32x4 rb{};
   if (EPI == kEpiResidual && bias) rb = *reinterpret_cast<const u32x4*>(bias + n0 + cc * 8);
@@ -354,9 +227,6 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt_kernel(const uint16_t* __
     for (int e = 0; e < 8; ++e) cssq[e] = 0.f;
     st_k = *reinterpret_cast<const u32x4*>(Cs + cc * 16);
   }
-  // rows tid / CPR + (kThreads / CPR)·i; each batch's LDS reads issued before its stores (rows past M
-  // read row rows_valid - 1 and are skipped): a read-then-use per row compiled to one ds_read +
-  // s_waitcnt lgkmcnt(0) round trip per row
   auto out_row = [&](int row, u32x4 v) {
     int64_t off = (int64_t)(m0 + row) * N + n0 + cc * 8;
     if constexpr (MODE == kModeDgS2) {  // dY-grid pixel (b, i, j) -> dX pixel (b, 2i + ph, 2j + pw)
@@ -398,35 +268,20 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt_kernel(const uint16_t* __
       // y = res + (A·Bᵀ, already rounded to bf16 in the C tile) [+ bias]: one extra rounding of
       // the product against addmm_'s single one (the residual term dominates the sum)
       const u32x4 r = *reinterpret_cast<const u32x4*>(res + (int64_t)(m0 + row) * ldr + n0 + cc * 8);
+      if (bias) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float lo = bf(r[e] & 0xffffu) + bf(v[e] & 0xffffu), hi = bf(r[e] >> 16) + bf(v[e] >> 16);
-        if (bias) {
-          lo += bf(rb[e] & 0xffffu);
-          hi += bf(rb[e] >> 16);
-        }
-        v[e] = dev::pack_bf16x2(lo, hi);
+        for (int e = 0; e < 4; ++e)
+          v[e] = dev::pack_bf16x2(bf(r[e] & 0xffffu) + bf(v[e] & 0xffffu) + bf(rb[e] & 0xffffu),
+                                  bf(r[e] >> 16) + bf(v[e] >> 16) + bf(rb[e] >> 16));
+      } else {
+        v = add_bf16x8(r, v);
       }
       *reinterpret_cast<u32x4*>(Y + off) = v;
     } else {
       *reinterpret_cast<u32x4*>(Y + off) = v;
     }
   };
-  constexpr int NIT = kBM * CPR / kThreads, RSTR = kThreads / CPR, EB = NIT < 4 ? NIT : 4;
-  static_assert(kBM * CPR % kThreads == 0, "readout rows must divide evenly over the threads");
-#pragma unroll
-  for (int i0 = 0; i0 < NIT; i0 += EB) {
-    u32x4 vv[EB];
-#pragma unroll
-    for (int j = 0; j < EB; ++j)
-      if (i0 + j < NIT)
-        vv[j] = *reinterpret_cast<const u32x4*>(Cs + min(tid / CPR + RSTR * (i0 + j), rows_valid - 1) * CST + cc * 16);
-#pragma unroll
-    for (int j = 0; j < EB; ++j) {
-      const int row = tid / CPR + RSTR * (i0 + j);
-      if (i0 + j < NIT && row < rows_valid) out_row(row, vv[j]);
-    }
-  }
+  readout_rows<BN>(Cs, tid, rows_valid, out_row);
   if (EPI == kEpiStats) {
     // lanes sharing cc (xor over the lane bits above log2(CPR)), then the waves through LDS; one
     // (count, mean, M2) per channel and tile, group-minor: part[q][N][mtiles] (bn_stats_from_partials)
@@ -489,29 +344,13 @@ void launch_gemm(const at::Tensor& a, const at::Tensor& b, uint16_t* y, uint16_t
                  const uint16_t* res, float* part, int64_t ldr, int M, int N, int K, hipStream_t stream,
                  const ConvGeo& cg = ConvGeo{}) {
   const int mtiles = (M + kBM - 1) / kBM, ntiles = N / BN, phases = MODE == kModeDgS2 ? 4 : 1;
-  // stages | C tile (+ the column-sum exchange of the dGELU epilogue)
-  const size_t lds = std::max<size_t>((size_t)2 * (kBM + BN) * 128,
-                                      (size_t)kBM * (BN * 2 + 16) + (EPI == kEpiDGelu ? (size_t)2048 * NW : 0));
-  static bool attr = false;
-  if (!attr) {
-    XDDP_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_nt_kernel<BN, EPI, MODE>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
+  // (+ the column-sum exchange of the dGELU epilogue past the C tile)
+  const size_t lds = TileGeo<BN>::lds_bytes(EPI == kEpiDGelu ? (size_t)2048 * NW : 0);
+  max_dyn_lds_once<gemm_nt_kernel<BN, EPI, MODE>>(lds);
   hipLaunchKernelGGL((gemm_nt_kernel<BN, EPI, MODE>), dim3(phases * mtiles * ntiles), dim3(kThreads), lds, stream,
                      reinterpret_cast<const uint16_t*>(a.data_ptr()), reinterpret_cast<const uint16_t*>(b.data_ptr()),
                      y, y2, bias, res, part, M, N, K, ntiles, ldr, cg);
   XDDP_HIP_CHECK(hipGetLastError());
-}
-
-// Tile width: 256 x 256 unless the 256 x 128 grid fills the CUs' last round better (one block
-// per CU: a 256 x 256 grid of 800 tiles on 256 CUs runs 4 rounds, the last 1/8 full).
-int pick_bn(int64_t M, int64_t N, int cus) {
-  if (N % 256) return 128;
-  const int64_t mt = (M + kBM - 1) / kBM;
-  const int64_t r256 = (mt * (N / 256) + cus - 1) / cus, r128 = (mt * (N / 128) + cus - 1) / cus;
-  // a 256 x 128 tile does half the work at ~1.15x the per-FLOP cost (more B traffic per MFMA)
-  return 2.0 * r256 <= 1.15 * r128 ? 256 : 128;
 }
 
 }  // namespace
@@ -566,19 +405,7 @@ std::vector<at::Tensor> gemm_nt(const at::Tensor& a, const at::Tensor& w, const 
   }
   at::Tensor y2 = epi == 2 ? at::empty({M, N}, a.options()) : at::Tensor();
   auto stream = c10::hip::getCurrentHIPStream(a.device().index()).stream();
-  int cus = 256;
-  {
-    static int cached = 0;
-    if (!cached) {
-      int v = 0;
-      if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, a.device().index()) == hipSuccess && v > 0)
-        cached = v;
-      else
-        cached = 256;
-    }
-    cus = cached;
-  }
-  const int BN = pick_bn(M, N, cus);
+  const int BN = pick_bn(M, N, cu_count(a.device().index()));
   auto* yp = reinterpret_cast<uint16_t*>(y.data_ptr());
   auto* y2p = epi == 2 ? reinterpret_cast<uint16_t*>(y2.data_ptr()) : nullptr;
   const auto* bp = has_bias ? reinterpret_cast<const uint16_t*>(bias->data_ptr()) : nullptr;

@@ -51,9 +51,12 @@ __global__ __launch_bounds__(kXT) void xent_fwd_kernel(const dev::bf16_t* __rest
 #pragma unroll
     for (int j = 1; j < 8; ++j) vm = fmaxf(vm, v[j]);
     const float M = fmaxf(m, vm);
-    float acc = s * __expf(m - M);
+    // nothing finite yet (masked logits, -inf in whole chunks): subtract 0, so every term is
+    // exp(-inf) = 0 and not exp(-inf + inf) = NaN; one select per 8 logits, as in merge()
+    const float Ms = M == -INFINITY ? 0.f : M;
+    float acc = s * __expf(m - Ms);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc += __expf(v[j] - M);
+    for (int j = 0; j < 8; ++j) acc += __expf(v[j] - Ms);
     m = M;
     s = acc;
   }

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void swiglu_bwd_kernel(const T* __restrict_
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float s = 1.f / (1.f + __expf(-x[j]));
-      ob[j] = gg[j] * x[j] * s;
+      ob[j] = gg[j] * (x[j] * s);  // silu first: g * a may overflow where a * s is 0 (inf * 0 = NaN)
       oa[j] = gg[j] * z[j] * s * fmaf(x[j], 1.f - s, 1.f);
     }
     Vec8<T>::st(da + v * 8, oa);

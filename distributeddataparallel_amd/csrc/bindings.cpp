@@ -436,6 +436,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       }, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"), py::arg("masters"),
       py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"), py::arg("step"),
       py::arg("decoupled"), py::arg("maximize"), py::arg("grad_scale") = py::none());
+  m.def("fused_adam8", [](const std::vector<at::Tensor>& p, const std::vector<at::Tensor>& g,
+                          const std::vector<at::Tensor>& mq, const std::vector<at::Tensor>& ms,
+                          const std::vector<at::Tensor>& sq, const std::vector<at::Tensor>& ss,
+                          const std::vector<at::Tensor>& masters, const std::vector<int64_t>& ordinals,
+                          const std::vector<int64_t>& group_offsets, double lr, double b1, double b2, double eps,
+                          double wd, int64_t step, int64_t seed, bool decoupled, bool maximize,
+                          c10::optional<at::Tensor> gs) {
+        if (p.empty()) return;
+        kernels::fused_adam8(p, g, mq, ms, sq, ss, masters, ordinals, group_offsets, lr, b1, b2, eps, wd, step, seed,
+                             decoupled, maximize, gs, stream_of(p[0]));
+      }, py::arg("params"), py::arg("grads"), py::arg("exp_avg_q"), py::arg("exp_avg_scale"),
+      py::arg("exp_avg_sq_q"), py::arg("exp_avg_sq_scale"), py::arg("masters"), py::arg("ordinals"),
+      py::arg("group_offsets"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+      py::arg("weight_decay"), py::arg("step"), py::arg("seed"), py::arg("decoupled"), py::arg("maximize"),
+      py::arg("grad_scale") = py::none());
 
   kernels::bind_norm_kernels(m);
 }

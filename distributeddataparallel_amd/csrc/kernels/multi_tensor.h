@@ -59,5 +59,19 @@ void fused_adam(const std::vector<at::Tensor>& params, const std::vector<at::Ten
                 double weight_decay, int64_t step, bool decoupled, bool maximize,
                 const c10::optional<at::Tensor>& grad_scale, hipStream_t stream);
 
+// fused_adam with 8-bit moments: per parameter (or 128-aligned range of one) uint8 e4m3 codes of
+// exp_avg and of sqrt(exp_avg_sq) (numel each, memory order) and one fp32 scale per 128 elements
+// (= group max / 448). The moments are dequantised, updated exactly as in fused_adam, and
+// re-quantised with stochastic rounding whose random bits hash (seed, ordinals[i], step, element
+// index within the parameter = group_offsets[i] * 128 + position, moment). A range must start at a
+// group boundary of its parameter and may end short only at the parameter's end.
+void fused_adam8(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                 const std::vector<at::Tensor>& m_q, const std::vector<at::Tensor>& m_scale,
+                 const std::vector<at::Tensor>& s_q, const std::vector<at::Tensor>& s_scale,
+                 const std::vector<at::Tensor>& masters, const std::vector<int64_t>& ordinals,
+                 const std::vector<int64_t>& group_offsets, double lr, double beta1, double beta2, double eps,
+                 double weight_decay, int64_t step, int64_t seed, bool decoupled, bool maximize,
+                 const c10::optional<at::Tensor>& grad_scale, hipStream_t stream);
+
 }  // namespace kernels
 }  // namespace xddp

@@ -840,5 +840,309 @@ void fused_adam(const std::vector<at::Tensor>& params, const std::vector<at::Ten
   }));
 }
 
+// ------------------------------------------------------------------------------------
+// Fused Adam / AdamW with 8-bit moments: slots {param, grad, m codes, m scales, s codes, s scales,
+// master, parameter ordinal, element offset of the range within its parameter}
+//
+// Both moments are OCP e4m3 codes with one fp32 scale per group of 128 consecutive elements
+// (scale = group max / 448); the second moment is stored as s = sqrt(v). A block's 8192-element chunk
+// is 64 whole groups, and a group is 16 adjacent lanes x 8 elements, so the two group maxima are
+// reduced over a DPP row (no LDS, no barrier). The update itself is adam_kernel's `upd`, on the
+// dequantised fp32 moments; the parameter uses the fresh fp32 moments, which are re-quantised
+// afterwards with stochastic rounding (v_cvt_sr_fp8_f32). The random bits are a stateless hash of
+// (seed, parameter ordinal, step, element index within the parameter, moment), so they do not
+// depend on the launch, the segment table, the load path or on slicing. Loads and stores differ
+// between the vector path, the tail and the unaligned path; everything in between is one function.
+// ------------------------------------------------------------------------------------
+constexpr int kQGroup = 128;
+constexpr float kE4M3Max = 448.f;
+static_assert(kChunk % kQGroup == 0 && kQGroup == 16 * 8, "a group is one DPP row of 8-element lanes");
+static_assert(sizeof(SegTable<9>) + 128 <= 4096, "the by-value segment table must fit the kernarg segment");
+
+__device__ __forceinline__ uint32_t mix32(uint32_t x) {  // 2-round multiply-xorshift finalizer
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  return x ^ (x >> 16);
+}
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_max(float v) {
+  return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true)));
+}
+// max over the 16 lanes of a DPP row, result in every lane (inputs are >= 0)
+__device__ __forceinline__ float row16_max(float v) {
+  v = dpp_max<0xB1>(v);   // quad_perm:[1,0,3,2]
+  v = dpp_max<0x4E>(v);   // quad_perm:[2,3,0,1]
+  v = dpp_max<0x141>(v);  // row_half_mirror
+  return dpp_max<0x140>(v);  // row_mirror
+}
+
+__device__ __forceinline__ void e4m3x4_decode(uint32_t w, float* f) {
+  f[0] = __builtin_amdgcn_cvt_f32_fp8((int)w, 0);
+  f[1] = __builtin_amdgcn_cvt_f32_fp8((int)w, 1);
+  f[2] = __builtin_amdgcn_cvt_f32_fp8((int)w, 2);
+  f[3] = __builtin_amdgcn_cvt_f32_fp8((int)w, 3);
+}
+// four stochastically rounded e4m3 codes of q[0..3] (already within +-448), random words r[0..3]
+__device__ __forceinline__ uint32_t e4m3x4_sr(const float* q, const uint32_t* r) {
+  int w = 0;
+  w = __builtin_amdgcn_cvt_sr_fp8_f32(q[0], (int)r[0], w, 0);
+  w = __builtin_amdgcn_cvt_sr_fp8_f32(q[1], (int)r[1], w, 1);
+  w = __builtin_amdgcn_cvt_sr_fp8_f32(q[2], (int)r[2], w, 2);
+  w = __builtin_amdgcn_cvt_sr_fp8_f32(q[3], (int)r[3], w, 3);
+  return (uint32_t)w;
+}
+
+// Re-quantise one lane's 8 fresh moments (m, s = sqrt(v); zeros past the end of the range). `idx` is
+// the first element's index within its parameter, km / ks the two moments' hash keys.
+__device__ __forceinline__ void adam8_quantize(const float (&m)[8], const float (&sv)[8], int64_t idx, uint32_t km,
+                                               uint32_t ks, uint32_t (&mq)[2], uint32_t (&sq)[2], float& msc,
+                                               float& ssc) {
+  float am = 0.f, as = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    am = fmaxf(am, fabsf(m[j]));
+    as = fmaxf(as, sv[j]);
+  }
+  msc = row16_max(am) / kE4M3Max;
+  ssc = row16_max(as) / kE4M3Max;
+  // (a scale below the smallest normal float, |m| < 5.3e-36, has no finite inverse: such a group
+  // keeps its scale and gets zero codes; s = sqrt(v) >= 3.7e-23 never comes near it)
+  const float im = msc >= 1.17549435e-38f ? 1.f / msc : 0.f;
+  const float is = ssc >= 1.17549435e-38f ? 1.f / ssc : 0.f;
+  const uint32_t lo = (uint32_t)idx, hi = (uint32_t)((uint64_t)idx >> 32) * 0x9e3779b9u;
+  float qm[8], qs[8];
+  uint32_t rm[8], rs[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    qm[j] = fminf(fmaxf(m[j] * im, -kE4M3Max), kE4M3Max);
+    qs[j] = fminf(sv[j] * is, kE4M3Max);
+    rm[j] = mix32((lo + j) ^ km ^ hi);
+    rs[j] = mix32((lo + j) ^ ks ^ hi);
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    mq[h] = e4m3x4_sr(qm + 4 * h, rm + 4 * h);
+    uint32_t w = e4m3x4_sr(qs + 4 * h, rs + 4 * h);
+    // a live element never gets code 0 (it would reach m / (0 + eps)): up to the smallest code
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+      if (sv[4 * h + b] > 0.f && ((w >> (8 * b)) & 0xffu) == 0u) w |= 1u << (8 * b);
+    sq[h] = w;
+  }
+}
+
+template <typename P, typename G, bool VEC, bool MASTER>
+__global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr, float b1, float b2, float eps,
+                                                         float wd, float bc1, float bc2_sqrt, bool decoupled,
+                                                         bool maximize, const float* gs, unsigned long long seed,
+                                                         uint32_t step) {
+  const int s = find_seg(t, blockIdx.x);
+  const int64_t blk = blockIdx.x - (s ? t.blk_end[s - 1] : 0);
+  P* p = reinterpret_cast<P*>(t.ptr[0][s]);
+  const G* g = reinterpret_cast<const G*>(t.ptr[1][s]);
+  uint8_t* mqp = reinterpret_cast<uint8_t*>(t.ptr[2][s]);
+  float* msp = reinterpret_cast<float*>(t.ptr[3][s]);
+  uint8_t* sqp = reinterpret_cast<uint8_t*>(t.ptr[4][s]);
+  float* ssp = reinterpret_cast<float*>(t.ptr[5][s]);
+  float* mp = reinterpret_cast<float*>(t.ptr[6][s]);
+  const unsigned long long ordinal = reinterpret_cast<uintptr_t>(t.ptr[7][s]);
+  const int64_t eoff = (int64_t)reinterpret_cast<uintptr_t>(t.ptr[8][s]);
+  const int64_t n = t.numel[s];
+  const unsigned long long key = mix64(seed ^ mix64((ordinal << 32) | step));
+  const uint32_t km = (uint32_t)key, ks = (uint32_t)(key >> 32);
+  const float gscale = (gs ? *gs : 1.f) * (maximize ? -1.f : 1.f);
+  const float step_size = lr / bc1;
+  const int64_t base = blk * kChunk;
+  const bool lead = (threadIdx.x & 15) == 0;  // the lane that writes its group's two scales
+  auto upd = [&](float& pv, float gv, float& mv, float& vv) {
+    float gg = gv * gscale;
+    if (wd != 0.f) {
+      if (decoupled) pv *= (1.f - lr * wd);
+      else gg = fmaf(wd, pv, gg);
+    }
+    mv = fmaf(b1, mv, (1.f - b1) * gg);
+    vv = fmaf(b2, vv, (1.f - b2) * gg * gg);
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    pv = pv - step_size * mv / denom;
+  };
+  // dequantise, update, re-quantise one lane's 8 elements, the first `nv` of which exist
+  auto update8 = [&](int64_t i, int nv, float (&pv)[8], const float (&gv)[8], uint32_t (&mq)[2], uint32_t (&sq)[2],
+                     float& msc, float& ssc) {
+    float m[8], sv[8];
+    e4m3x4_decode(mq[0], m);
+    e4m3x4_decode(mq[1], m + 4);
+    e4m3x4_decode(sq[0], sv);
+    e4m3x4_decode(sq[1], sv + 4);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float mv = m[j] * msc, sh = sv[j] * ssc;
+      float vv = sh * sh;
+      upd(pv[j], gv[j], mv, vv);
+      m[j] = j < nv ? mv : 0.f;
+      sv[j] = j < nv ? sqrtf(vv) : 0.f;
+    }
+    adam8_quantize(m, sv, eoff + i, km, ks, mq, sq, msc, ssc);
+  };
+  if (VEC && base + kChunk <= n) {
+    // whole chunk: every iteration's loads first, then the updates and stores (as adam_kernel)
+    float pv[kIters][8], gv[kIters][8], msc[kIters], ssc[kIters];
+    uint32_t mq[kIters][2], sq[kIters][2];
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+      if (MASTER) Vec8<float>::ld(mp + i, pv[it]); else Vec8<P>::ld(p + i, pv[it]);
+      Vec8<G>::ld(g + i, gv[it]);
+      const uint2 a = *reinterpret_cast<const uint2*>(mqp + i), b = *reinterpret_cast<const uint2*>(sqp + i);
+      mq[it][0] = a.x; mq[it][1] = a.y;
+      sq[it][0] = b.x; sq[it][1] = b.y;
+      msc[it] = msp[i / kQGroup];
+      ssc[it] = ssp[i / kQGroup];
+    }
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+      update8(i, 8, pv[it], gv[it], mq[it], sq[it], msc[it], ssc[it]);
+      Vec8<P>::st(p + i, pv[it]);
+      if (MASTER) Vec8<float>::st(mp + i, pv[it]);
+      *reinterpret_cast<uint2*>(mqp + i) = make_uint2(mq[it][0], mq[it][1]);
+      *reinterpret_cast<uint2*>(sqp + i) = make_uint2(sq[it][0], sq[it][1]);
+      if (lead) {
+        msp[i / kQGroup] = msc[it];
+        ssp[i / kQGroup] = ssc[it];
+      }
+    }
+    return;
+  }
+  // the range's last chunk, or unaligned pointers. Every lane runs every iteration, also past the
+  // end (with zeros), so the row reductions always see 16 live lanes.
+#pragma unroll 1
+  for (int it = 0; it < kIters; ++it) {
+    const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+    const int nv = (int)std::min<int64_t>(std::max<int64_t>(n - i, 0), 8);
+    const int64_t grp = i / kQGroup;
+    const bool live = grp * kQGroup < n;  // the group has at least one element
+    float pv[8], gv[8], msc = 0.f, ssc = 0.f;
+    uint32_t mq[2] = {0u, 0u}, sq[2] = {0u, 0u};
+    if (VEC && nv == 8) {
+      if (MASTER) Vec8<float>::ld(mp + i, pv); else Vec8<P>::ld(p + i, pv);
+      Vec8<G>::ld(g + i, gv);
+      const uint2 a = *reinterpret_cast<const uint2*>(mqp + i), b = *reinterpret_cast<const uint2*>(sqp + i);
+      mq[0] = a.x; mq[1] = a.y;
+      sq[0] = b.x; sq[1] = b.y;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        pv[j] = gv[j] = 0.f;
+        if (j < nv) {
+          pv[j] = MASTER ? mp[i + j] : Elem<P, float>::ld(p, i + j);
+          gv[j] = Elem<G, float>::ld(g, i + j);
+          mq[j >> 2] |= (uint32_t)mqp[i + j] << (8 * (j & 3));
+          sq[j >> 2] |= (uint32_t)sqp[i + j] << (8 * (j & 3));
+        }
+      }
+    }
+    if (live) {
+      msc = msp[grp];
+      ssc = ssp[grp];
+    }
+    update8(i, nv, pv, gv, mq, sq, msc, ssc);
+    if (VEC && nv == 8) {
+      Vec8<P>::st(p + i, pv);
+      if (MASTER) Vec8<float>::st(mp + i, pv);
+      *reinterpret_cast<uint2*>(mqp + i) = make_uint2(mq[0], mq[1]);
+      *reinterpret_cast<uint2*>(sqp + i) = make_uint2(sq[0], sq[1]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (j < nv) {
+          Elem<P, float>::st(p, i + j, pv[j]);
+          if (MASTER) mp[i + j] = pv[j];
+          mqp[i + j] = (uint8_t)(mq[j >> 2] >> (8 * (j & 3)));
+          sqp[i + j] = (uint8_t)(sq[j >> 2] >> (8 * (j & 3)));
+        }
+      }
+    }
+    if (lead && live) {
+      msp[grp] = msc;
+      ssp[grp] = ssc;
+    }
+  }
+}
+
+void fused_adam8(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                 const std::vector<at::Tensor>& m_q, const std::vector<at::Tensor>& m_scale,
+                 const std::vector<at::Tensor>& s_q, const std::vector<at::Tensor>& s_scale,
+                 const std::vector<at::Tensor>& masters, const std::vector<int64_t>& ordinals,
+                 const std::vector<int64_t>& group_offsets, double lr, double beta1, double beta2, double eps,
+                 double weight_decay, int64_t step, int64_t seed, bool decoupled, bool maximize,
+                 const c10::optional<at::Tensor>& grad_scale, hipStream_t stream) {
+  const size_t N = params.size();
+  TORCH_CHECK(grads.size() == N && m_q.size() == N && m_scale.size() == N && s_q.size() == N && s_scale.size() == N &&
+                  ordinals.size() == N && group_offsets.size() == N,
+              "adam8: list length mismatch");
+  const bool has_master = !masters.empty();
+  TORCH_CHECK(!has_master || masters.size() == N, "adam8: masters length mismatch");
+  if (N == 0) return;
+  TORCH_CHECK(step >= 1 && step <= (int64_t)UINT32_MAX, "adam8: step must be in [1, 2^32)");
+  const auto pt = params[0].scalar_type(), gt = grads[0].scalar_type();
+  TORCH_CHECK(pt != at::kDouble && gt != at::kDouble, "fused Adam: fp64 unsupported");
+  std::vector<std::array<void*, 9>> ptrs;
+  std::vector<int64_t> numels;
+  bool vec = true;
+  for (size_t i = 0; i < N; ++i) {
+    const int64_t n = params[i].numel(), ng = (n + kQGroup - 1) / kQGroup;
+    TORCH_CHECK(params[i].is_cuda() && params[i].scalar_type() == pt && grads[i].scalar_type() == gt,
+                "adam8: device tensors of one dtype per list expected");
+    check_dense_pair(params[i], grads[i]);
+    for (const at::Tensor* q : {&m_q[i], &s_q[i]})
+      TORCH_CHECK(q->is_cuda() && q->scalar_type() == at::kByte && q->is_contiguous() && q->numel() == n,
+                  "adam8: moment codes must be contiguous uint8 device tensors of the parameter's numel");
+    for (const at::Tensor* q : {&m_scale[i], &s_scale[i]})
+      TORCH_CHECK(q->is_cuda() && q->scalar_type() == at::kFloat && q->is_contiguous() && q->numel() == ng,
+                  "adam8: moment scales must be contiguous fp32 device tensors, one entry per 128 elements");
+    TORCH_CHECK(ordinals[i] >= 0 && ordinals[i] <= (int64_t)UINT32_MAX && group_offsets[i] >= 0,
+                "adam8: bad parameter ordinal or group offset");
+    void* mp = nullptr;
+    if (has_master) {
+      TORCH_CHECK(masters[i].is_cuda() && masters[i].scalar_type() == at::kFloat, "master weights must be fp32");
+      check_dense_pair(params[i], masters[i]);
+      mp = masters[i].data_ptr();
+    }
+    ptrs.push_back({params[i].data_ptr(), const_cast<void*>(grads[i].data_ptr()), m_q[i].data_ptr(),
+                    m_scale[i].data_ptr(), s_q[i].data_ptr(), s_scale[i].data_ptr(), mp,
+                    reinterpret_cast<void*>((uintptr_t)ordinals[i]),
+                    reinterpret_cast<void*>((uintptr_t)(group_offsets[i] * kQGroup))});
+    numels.push_back(n);
+    vec = vec && aligned16(params[i].data_ptr()) && aligned16(grads[i].data_ptr()) && aligned16(mp) &&
+          (reinterpret_cast<uintptr_t>(m_q[i].data_ptr()) & 7u) == 0 &&
+          (reinterpret_cast<uintptr_t>(s_q[i].data_ptr()) & 7u) == 0;
+  }
+  const double bc1 = 1.0 - std::pow(beta1, (double)step);
+  const double bc2 = 1.0 - std::pow(beta2, (double)step);
+  const float* gs = scale_ptr(grad_scale);
+  // (no fp64 instantiations: the dtype check above has already refused them)
+#define XDDP_DISPATCH_ADAM8(st, NAME, ...)                           \
+  switch (st) {                                                      \
+    case at::kFloat: { using NAME = float; __VA_ARGS__; break; }     \
+    case at::kBFloat16: { using NAME = bf16_t; __VA_ARGS__; break; } \
+    case at::kHalf: { using NAME = f16_t; __VA_ARGS__; break; }      \
+    default: TORCH_CHECK(false, "fused Adam (8-bit states): unsupported dtype ", st); \
+  }
+  XDDP_DISPATCH_ADAM8(pt, P, XDDP_DISPATCH_ADAM8(gt, G, {
+    for_each_table<9>(ptrs, numels, [&](const SegTable<9>& t, int32_t nb) {
+      auto k = vec ? (has_master ? adam8_kernel<P, G, true, true> : adam8_kernel<P, G, true, false>)
+                   : (has_master ? adam8_kernel<P, G, false, true> : adam8_kernel<P, G, false, false>);
+      hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t, (float)lr, (float)beta1, (float)beta2,
+                         (float)eps, (float)weight_decay, (float)bc1, (float)std::sqrt(bc2), decoupled, maximize, gs,
+                         (unsigned long long)seed, (uint32_t)step);
+      XDDP_HIP_CHECK(hipGetLastError());
+    });
+  }));
+#undef XDDP_DISPATCH_ADAM8
+}
+
 }  // namespace kernels
 }  // namespace xddp

@@ -11,6 +11,7 @@ CPU tensors take an equivalent torch reference path (the GPU-free test backend).
 """
 from __future__ import annotations
 
+import functools
 from collections import defaultdict
 from typing import Iterable, List, Optional
 
@@ -40,7 +41,82 @@ def _flat_range(t: torch.Tensor, lo: int, hi: int) -> torch.Tensor:
     return t.as_strided((hi - lo,), (1,), t.storage_offset() + lo)
 
 
-class FusedSGD(Optimizer):
+_QGROUP = 128      # elements per scale of the 8-bit optimizer states
+_E4M3_MAX = 448.0
+_FLT_MIN = 1.17549435e-38
+
+
+@functools.lru_cache(maxsize=None)
+def _e4m3_table(device) -> torch.Tensor:
+    """Value of every OCP e4m3 code (256 entries, built in software; 0x7f / 0xff are NaN). The
+    first 127 entries are the non-negative grid in ascending order, so a code is its own index."""
+    vals = []
+    for code in range(128):
+        e, m = code >> 3, code & 7
+        vals.append(m * 2.0 ** -9 if e == 0 else (1 + m / 8) * 2.0 ** (e - 7))
+    vals[127] = float("nan")
+    return torch.tensor(vals + [-v for v in vals], dtype=torch.float32, device=device)
+
+
+def _mix64(z: int) -> int:  # splitmix64 finalizer
+    z &= (1 << 64) - 1
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & ((1 << 64) - 1)
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & ((1 << 64) - 1)
+    return z ^ (z >> 31)
+
+
+def _group_expand(scale: torch.Tensor, n: int) -> torch.Tensor:
+    return scale.repeat_interleave(_QGROUP)[:n]
+
+
+def _dequantize_e4m3(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    return _e4m3_table(codes.device)[codes.long()] * _group_expand(scale, codes.numel())
+
+
+def _quantize_e4m3_sr(x: torch.Tensor, u: torch.Tensor, nonneg: bool):
+    """Block-scaled e4m3 codes of the 1-D fp32 ``x`` (which starts at a group boundary), rounded
+    stochastically with the uniform [0, 1) numbers ``u``: (uint8 codes, fp32 scale per group)."""
+    n = x.numel()
+    ng = (n + _QGROUP - 1) // _QGROUP
+    ax = x.abs()
+    amax = torch.nn.functional.pad(ax, (0, ng * _QGROUP - n)).view(ng, _QGROUP).amax(1)
+    scale = amax / _E4M3_MAX
+    inv = torch.where(scale >= _FLT_MIN, 1.0 / scale, torch.zeros_like(scale))
+    q = (ax * _group_expand(inv, n)).clamp_(max=_E4M3_MAX)
+    grid = _e4m3_table(x.device)[:127]
+    idx = torch.searchsorted(grid, q, right=True) - 1  # grid[idx] <= q < grid[idx + 1]
+    lo, hi = grid[idx], grid[(idx + 1).clamp_(max=126)]
+    up = torch.where(hi > lo, (q - lo) / (hi - lo), torch.zeros_like(q))
+    code = idx + (u < up)
+    if nonneg:  # a live element never gets code 0
+        code = torch.where((x > 0) & (code == 0), torch.ones_like(code), code)
+    else:
+        code = code + 128 * torch.signbit(x)
+    return code.to(torch.uint8), scale
+
+
+class _KeepStateDtypes:
+    """``load_state_dict`` that keeps every state tensor's saved dtype. torch's casts each of them
+    to the parameter's dtype, which for a bf16 model rounds the fp32 moments, momentum buffers and
+    master weights to bf16 (the fused kernels then reject them) and would turn the 8-bit states'
+    uint8 codes and fp32 scales into bf16. State tensors only move to the parameter's device."""
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        saved_ids = [k for g in state_dict["param_groups"] for k in g["params"]]
+        params = [p for g in self.param_groups for p in g["params"]]
+        for k, p in zip(saved_ids, params):
+            for key, val in state_dict["state"].get(k, {}).items():
+                if isinstance(val, torch.Tensor) and key != "step":
+                    self.state[p][key] = val.to(device=p.device)
+        for g in self.param_groups:
+            for key, val in self.defaults.items():
+                g.setdefault(key, val)  # a checkpoint from before an option existed
+        for cache in ("_group_of", "_ordinal_of"):
+            self.__dict__.pop(cache, None)
+
+
+class FusedSGD(_KeepStateDtypes, Optimizer):
     """SGD with momentum/dampening/Nesterov/weight decay (torch.optim.SGD semantics).
 
     ``master_weights=True`` keeps fp32 master copies for low-precision params.
@@ -117,18 +193,44 @@ class FusedSGD(Optimizer):
             p.copy_(p.float() - lr * d)
 
 
-class FusedAdamW(Optimizer):
-    """Adam / AdamW (decoupled weight decay) with fp32 moments (torch.optim semantics, no amsgrad)."""
+class FusedAdamW(_KeepStateDtypes, Optimizer):
+    """Adam / AdamW (decoupled weight decay), torch.optim semantics, no amsgrad.
+
+    ``state_bits=32`` (default) keeps fp32 moments. ``state_bits=8`` keeps both moments as OCP e4m3
+    codes with one fp32 scale per group of 128 consecutive elements of the parameter in memory order
+    (the last group may be short): per parameter ``exp_avg_q`` / ``exp_avg_sq_q`` (uint8, ``numel``)
+    and ``exp_avg_scale`` / ``exp_avg_sq_scale`` (fp32, ``ceil(numel / 128)``), 2.06 instead of 8
+    bytes per parameter. A scale is its group's maximum / 448; the second moment is stored as
+    ``sqrt(exp_avg_sq)``, and a non-zero root never gets code 0. Each step dequantises the moments,
+    applies exactly the 32-bit update (the parameters and masters use the fresh fp32 moments) and
+    re-quantises with stochastic rounding: round-to-nearest would drop every change of less than
+    half a code step (a code step is 6.25 % of the value), so with ``beta2 = 0.999`` the second
+    moment could never decay. The random bits are a stateless hash of (``seed``, the parameter's
+    ordinal in the optimizer, its step, the element index, the moment): a run is reproducible, and
+    independent of how parameters are grouped into launches or sliced. The CPU path draws its bits
+    from a ``torch.Generator`` seeded from the same tuple, so it matches the GPU path in
+    distribution, not bit for bit. :meth:`decode_states` gives the moments back in fp32.
+
+    With ``state_bits=8`` a step cannot be captured into a HIP graph (``RuntimeError``): the step
+    count is a host value baked into the launch, and a replayed graph would round with the same
+    random bits forever.
+    """
 
     _decoupled = True
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 maximize: bool = False, master_weights: bool = False, amsgrad: bool = False):
+                 maximize: bool = False, master_weights: bool = False, amsgrad: bool = False, state_bits: int = 32,
+                 seed: int = 0):
         if amsgrad:
             raise NotImplementedError("amsgrad is not supported by the fused kernel")
+        if state_bits not in (8, 32):
+            raise ValueError(f"state_bits must be 32 or 8, got {state_bits!r}")
+        if not 0 <= int(seed) < 1 << 63:
+            raise ValueError("seed must be in [0, 2^63)")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, maximize=maximize,
-                        master_weights=master_weights)
+                        master_weights=master_weights, state_bits=state_bits, seed=int(seed))
         super().__init__(params, defaults)
+        self._slice_pos = {}  # 8-bit states: how far this step's pieces of a parameter have come
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale: Optional[torch.Tensor] = None):
@@ -136,9 +238,16 @@ class FusedAdamW(Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._refuse_capture()
         C = load()
         for group in self.param_groups:
             b1, b2 = group["betas"]
+            if group["state_bits"] == 8:
+                items = [(p, p.grad, 0, p.numel()) for p in group["params"] if p.grad is not None]
+                for p, *_ in items:
+                    self._init_state(p, group)["step"] += 1
+                self._step8(group, items, grad_scale)
+                continue
             buckets = defaultdict(lambda: ([], [], [], [], [], []))
             for p in group["params"]:
                 if p.grad is None:
@@ -172,8 +281,29 @@ class FusedAdamW(Optimizer):
             self._group_of = {id(q): gi for gi, grp in enumerate(self.param_groups) for q in grp["params"]}
         return self._group_of.get(id(p))
 
+    def _ordinal(self, p):
+        if not hasattr(self, "_ordinal_of"):
+            self._ordinal_of = {id(q): i for i, q in enumerate(q for grp in self.param_groups for q in grp["params"])}
+        return self._ordinal_of[id(p)]
+
+    def _refuse_capture(self):
+        if (torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+                and any(g["state_bits"] == 8 for g in self.param_groups)):
+            raise RuntimeError("FusedAdamW(state_bits=8) cannot be captured into a HIP graph: the step count that "
+                               "seeds the stochastic rounding is a host value, so a replay would reuse one set of "
+                               "random bits; step outside the capture, or use state_bits=32")
+
     def _init_state(self, p, group):
         st = self.state[p]
+        if "step" not in st and group["state_bits"] == 8:
+            _flat_range(p, 0, p.numel())  # (raises for a parameter that is not dense)
+            ng = (p.numel() + _QGROUP - 1) // _QGROUP
+            st["step"] = 0
+            for name in ("exp_avg", "exp_avg_sq"):
+                st[name + "_q"] = torch.zeros(p.numel(), dtype=torch.uint8, device=p.device)
+                st[name + "_scale"] = torch.zeros(ng, dtype=torch.float32, device=p.device)
+            if group["master_weights"] and p.dtype in (torch.bfloat16, torch.float16):
+                st["master"] = p.detach().float().clone(memory_format=torch.preserve_format)
         if "step" not in st:
             st["step"] = 0
             st["exp_avg"] = _dense_like(p).zero_()
@@ -194,10 +324,12 @@ class FusedAdamW(Optimizer):
     def advance(self, params):
         """Start this step for ``params`` (state created on first use, step count + 1) without
         updating them; :meth:`step_slices` then updates them piecewise with that step count."""
+        self._refuse_capture()
         for p in params:
             gi = self._group_index(p)
             if gi is not None:
                 self._init_state(p, self.param_groups[gi])["step"] += 1
+                self._slice_pos[p] = 0
 
     @torch.no_grad()
     def step_slices(self, pieces):
@@ -206,7 +338,15 @@ class FusedAdamW(Optimizer):
         strides. Uses each param's current step count (:meth:`advance` first). AdamW is elementwise,
         so updating a param in several slices is bitwise the same as updating it at once — the
         overlapped optimizer steps a chunked tail bucket this way, chunk by chunk as each chunk's
-        all-reduce lands."""
+        all-reduce lands.
+
+        With ``state_bits=8`` a group of 128 elements can only be re-quantised once its whole
+        gradient is there, so within one step the pieces of a parameter must arrive in ascending,
+        contiguous order (the first at 0, each next one where the last ended; anything else raises),
+        and a piece ``[lo, hi)`` updates ``[lo // 128 * 128, hi // 128 * 128)``, or up to ``numel``
+        when ``hi == numel``: every group is updated by the piece that delivers its last element.
+        The result is still bitwise that of the whole-parameter update."""
+        self._refuse_capture()
         C = load()
         per_group = defaultdict(list)
         for p, g, lo, hi in pieces:
@@ -216,6 +356,21 @@ class FusedAdamW(Optimizer):
         for gi, items in per_group.items():
             group = self.param_groups[gi]
             b1, b2 = group["betas"]
+            if group["state_bits"] == 8:
+                ranges = []
+                for p, g, lo, hi in items:
+                    if self._init_state(p, group)["step"] == 0:
+                        raise RuntimeError("step_slices before advance() for this step")
+                    if lo != self._slice_pos.get(p, 0):
+                        raise RuntimeError(f"state_bits=8: a parameter's pieces must arrive in ascending, contiguous "
+                                           f"order within a step (expected one from {self._slice_pos.get(p, 0)}, got "
+                                           f"[{lo}, {hi}))")
+                    self._slice_pos[p] = hi
+                    lo, hi = lo // _QGROUP * _QGROUP, hi if hi == p.numel() else hi // _QGROUP * _QGROUP
+                    if hi > lo:
+                        ranges.append((p, g, lo, hi))
+                self._step8(group, ranges, None)
+                continue
             buckets = defaultdict(lambda: ([], [], [], [], [], []))
             for p, g, lo, hi in items:
                 st = self._init_state(p, group)
@@ -236,6 +391,62 @@ class FusedAdamW(Optimizer):
                                  step, self._decoupled, group["maximize"], None)
                 else:
                     self._cpu_step(ps, gs, m1, m2, masters, group, step, None)
+
+    def _step8(self, group, ranges, grad_scale):
+        """8-bit states: update ``ranges`` = ``[(param, grad, lo, hi)]``, ``lo`` a multiple of 128 and
+        ``hi`` one too or the parameter's numel, with each parameter's current step count."""
+        b1, b2 = group["betas"]
+        buckets = defaultdict(lambda: tuple([] for _ in range(9)))
+        for p, g, lo, hi in ranges:
+            st = self.state[p]
+            if g.stride() != p.stride() and not (g.is_contiguous() and p.is_contiguous()):
+                raise ValueError("state_bits=8 needs the gradient in the parameter's memory order")
+            b = buckets[_group_key(p, g) + (st["step"], "master" in st)]
+            glo, ghi = lo // _QGROUP, (hi + _QGROUP - 1) // _QGROUP
+            b[0].append(_flat_range(p, lo, hi))
+            b[1].append(_flat_range(g, lo, hi))
+            b[2].append(st["exp_avg_q"][lo:hi])
+            b[3].append(st["exp_avg_scale"][glo:ghi])
+            b[4].append(st["exp_avg_sq_q"][lo:hi])
+            b[5].append(st["exp_avg_sq_scale"][glo:ghi])
+            if "master" in st:
+                b[6].append(_flat_range(st["master"], lo, hi))
+            b[7].append(self._ordinal(p))
+            b[8].append((glo, p.numel()))
+        for (dev, pdt, gdt, step, has_master), (ps, gs, mq, ms, sq, ss, masters, ords, offs) in buckets.items():
+            if dev.type == "cuda":
+                load().fused_adam8(ps, gs, mq, ms, sq, ss, masters, ords, [o for o, _ in offs], group["lr"], b1, b2,
+                                   group["eps"], group["weight_decay"], step, group["seed"], self._decoupled,
+                                   group["maximize"], grad_scale)
+                continue
+            for i, (p, g) in enumerate(zip(ps, gs)):
+                n, (glo, numel) = p.numel(), offs[i]
+                m = _dequantize_e4m3(mq[i], ms[i])
+                v = _dequantize_e4m3(sq[i], ss[i]).square_()
+                self._cpu_step([p], [g], [m], [v], masters[i:i + 1], group, step, grad_scale)
+                for moment, x, codes, scales in ((0, m, mq[i], ms[i]), (1, v.sqrt_(), sq[i], ss[i])):
+                    gen = torch.Generator().manual_seed(
+                        _mix64(group["seed"] ^ _mix64((ords[i] << 32 | step) * 2 + moment)) >> 1)
+                    u = torch.rand(numel, generator=gen)[glo * _QGROUP:glo * _QGROUP + n]
+                    c, sc = _quantize_e4m3_sr(x, u, nonneg=moment == 1)
+                    codes.copy_(c)
+                    scales.copy_(sc)
+
+    @torch.no_grad()
+    def decode_states(self, p):
+        """``(exp_avg, exp_avg_sq)`` of parameter ``p`` as fp32 tensors of its shape and strides
+        (copies): the dequantised 8-bit states, or the fp32 states themselves."""
+        st = self.state[p]
+        if "exp_avg_q" not in st:
+            return st["exp_avg"].clone(memory_format=torch.preserve_format), \
+                st["exp_avg_sq"].clone(memory_format=torch.preserve_format)
+        out = []
+        for name, square in (("exp_avg", False), ("exp_avg_sq", True)):
+            x = _dequantize_e4m3(st[name + "_q"], st[name + "_scale"])
+            t = _dense_like(p)
+            _flat_range(t, 0, p.numel()).copy_(x * x if square else x)
+            out.append(t)
+        return tuple(out)
 
     def _cpu_step(self, ps, gs, m1, m2, masters, group, step, grad_scale):
         b1, b2 = group["betas"]
@@ -266,8 +477,8 @@ class FusedAdam(FusedAdamW):
     _decoupled = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, maximize=False,
-                 master_weights=False, amsgrad=False):
-        super().__init__(params, lr, betas, eps, weight_decay, maximize, master_weights, amsgrad)
+                 master_weights=False, amsgrad=False, state_bits=32, seed=0):
+        super().__init__(params, lr, betas, eps, weight_decay, maximize, master_weights, amsgrad, state_bits, seed)
 
 
 def grad_norm(parameters: Iterable[torch.Tensor], max_norm: float = 0.0) -> torch.Tensor:

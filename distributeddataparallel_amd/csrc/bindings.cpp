@@ -442,13 +442,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                           const std::vector<at::Tensor>& masters, const std::vector<int64_t>& ordinals,
                           const std::vector<int64_t>& group_offsets, double lr, double b1, double b2, double eps,
                           double wd, int64_t step, int64_t seed, bool decoupled, bool maximize,
-                          c10::optional<at::Tensor> gs) {
+                          c10::optional<at::Tensor> gs, bool stochastic_params) {
         if (p.empty()) return;
         kernels::fused_adam8(p, g, mq, ms, sq, ss, masters, ordinals, group_offsets, lr, b1, b2, eps, wd, step, seed,
-                             decoupled, maximize, gs, stream_of(p[0]));
+                             decoupled, maximize, gs, stochastic_params, stream_of(p[0]));
       }, py::arg("params"), py::arg("grads"), py::arg("exp_avg_q"), py::arg("exp_avg_scale"),
       py::arg("exp_avg_sq_q"), py::arg("exp_avg_sq_scale"), py::arg("masters"), py::arg("ordinals"),
       py::arg("group_offsets"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+      py::arg("weight_decay"), py::arg("step"), py::arg("seed"), py::arg("decoupled"), py::arg("maximize"),
+      py::arg("grad_scale") = py::none(), py::arg("stochastic_params") = false);
+  m.def("stochastic_round_bf16", [](const at::Tensor& x, at::Tensor out, int64_t seed, int64_t ordinal,
+                                    int64_t step, int64_t offset) {
+        kernels::stochastic_round_bf16(x, out, seed, ordinal, step, offset, stream_of(x));
+      }, py::arg("x"), py::arg("out"), py::arg("seed"), py::arg("ordinal") = 0, py::arg("step") = 0,
+      py::arg("offset") = 0, "out (bf16) = x (fp32) rounded stochastically with hashed random bits");
+  m.def("fused_adam_sr", [](const std::vector<at::Tensor>& p, const std::vector<at::Tensor>& g,
+                            const std::vector<at::Tensor>& m1, const std::vector<at::Tensor>& m2,
+                            const std::vector<int64_t>& ordinals, const std::vector<int64_t>& offsets, double lr,
+                            double b1, double b2, double eps, double wd, int64_t step, int64_t seed, bool decoupled,
+                            bool maximize, c10::optional<at::Tensor> gs) {
+        if (p.empty()) return;
+        kernels::fused_adam_sr(p, g, m1, m2, ordinals, offsets, lr, b1, b2, eps, wd, step, seed, decoupled, maximize,
+                               gs, stream_of(p[0]));
+      }, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"), py::arg("ordinals"),
+      py::arg("offsets"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
       py::arg("weight_decay"), py::arg("step"), py::arg("seed"), py::arg("decoupled"), py::arg("maximize"),
       py::arg("grad_scale") = py::none());
 

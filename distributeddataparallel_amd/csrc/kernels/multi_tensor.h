@@ -64,14 +64,31 @@ void fused_adam(const std::vector<at::Tensor>& params, const std::vector<at::Ten
 // (= group max / 448). The moments are dequantised, updated exactly as in fused_adam, and
 // re-quantised with stochastic rounding whose random bits hash (seed, ordinals[i], step, element
 // index within the parameter = group_offsets[i] * 128 + position, moment). A range must start at a
-// group boundary of its parameter and may end short only at the parameter's end.
+// group boundary of its parameter and may end short only at the parameter's end. With
+// `stochastic_params` (bf16 parameters, no masters) the parameters are written with the rounding of
+// stochastic_round_bf16, keyed by the same tuple.
 void fused_adam8(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
                  const std::vector<at::Tensor>& m_q, const std::vector<at::Tensor>& m_scale,
                  const std::vector<at::Tensor>& s_q, const std::vector<at::Tensor>& s_scale,
                  const std::vector<at::Tensor>& masters, const std::vector<int64_t>& ordinals,
                  const std::vector<int64_t>& group_offsets, double lr, double beta1, double beta2, double eps,
                  double weight_decay, int64_t step, int64_t seed, bool decoupled, bool maximize,
-                 const c10::optional<at::Tensor>& grad_scale, hipStream_t stream);
+                 const c10::optional<at::Tensor>& grad_scale, bool stochastic_params, hipStream_t stream);
+
+// out (bf16) = x (fp32, dense, same memory order) rounded stochastically: per element the upper half
+// of bits(x) + r, r the top 16 bits of a hash of (seed, ordinal, step, offset + index in memory
+// order); a finite value saturates instead of becoming inf, +-inf stay, NaN gives 0x7fc0.
+void stochastic_round_bf16(const at::Tensor& x, const at::Tensor& out, int64_t seed, int64_t ordinal, int64_t step,
+                           int64_t offset, hipStream_t stream);
+
+// fused_adam for bf16 parameters without masters (fp32 moments), the parameters written with the
+// rounding of stochastic_round_bf16 keyed by (seed, ordinals[i], step, offsets[i] + position):
+// offsets[i] is the element offset of the i-th range within its parameter.
+void fused_adam_sr(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                   const std::vector<at::Tensor>& exp_avgs, const std::vector<at::Tensor>& exp_avg_sqs,
+                   const std::vector<int64_t>& ordinals, const std::vector<int64_t>& offsets, double lr, double beta1,
+                   double beta2, double eps, double weight_decay, int64_t step, int64_t seed, bool decoupled,
+                   bool maximize, const c10::optional<at::Tensor>& grad_scale, hipStream_t stream);
 
 }  // namespace kernels
 }  // namespace xddp

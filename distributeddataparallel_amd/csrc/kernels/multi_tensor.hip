@@ -867,6 +867,33 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {  // 2-round multiply-xor
   return x ^ (x >> 16);
 }
 
+// Stochastically rounded bf16 parameter write. `key` is the hash key of (seed, ordinal, step) whose
+// low / high half are the moments' km / ks; the parameter write's key kp is the splitmix64 output
+// after it, a third stream.
+__device__ __forceinline__ uint32_t sr_param_key(unsigned long long key) {
+  return (uint32_t)mix64(key + 0x9e3779b97f4a7c15ull);
+}
+// bf16 bits of x rounded with the 16 random bits of element index e (within its parameter): the upper
+// half of (bits of x) + r, i.e. away from zero with probability (discarded bits) / 65536. A sum with
+// an all-ones exponent falls back to the upper half of x (a finite x saturates instead of becoming
+// inf, +-inf stay); NaN gives the quiet NaN 0x7fc0.
+__device__ __forceinline__ uint32_t sr_bf16(float x, int64_t e, uint32_t kp) {
+  const uint32_t u = __float_as_uint(x);
+  const uint32_t r = mix32((uint32_t)e ^ kp ^ ((uint32_t)((uint64_t)e >> 32) * 0x9e3779b9u)) >> 16;
+  uint32_t t = u + r;
+  if ((t & 0x7f800000u) == 0x7f800000u) t = u;
+  if ((u & 0x7fffffffu) > 0x7f800000u) t = 0x7fc00000u;
+  return t >> 16;
+}
+// 8 consecutive elements from index e0 on, one 16-byte store
+__device__ __forceinline__ void st8_sr_bf16(bf16_t* p, const float (&v)[8], int64_t e0, uint32_t kp) {
+  dev::u32x4 a;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    a[j] = sr_bf16(v[2 * j], e0 + 2 * j, kp) | (sr_bf16(v[2 * j + 1], e0 + 2 * j + 1, kp) << 16);
+  *reinterpret_cast<dev::u32x4*>(p) = a;
+}
+
 template <int CTRL>
 __device__ __forceinline__ float dpp_max(float v) {
   return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true)));
@@ -934,11 +961,13 @@ __device__ __forceinline__ void adam8_quantize(const float (&m)[8], const float 
   }
 }
 
-template <typename P, typename G, bool VEC, bool MASTER>
+// SR: bf16 parameters without a master, written with sr_bf16 (keyed like the moments, third stream).
+template <typename P, typename G, bool VEC, bool MASTER, bool SR = false>
 __global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr, float b1, float b2, float eps,
                                                          float wd, float bc1, float bc2_sqrt, bool decoupled,
                                                          bool maximize, const float* gs, unsigned long long seed,
                                                          uint32_t step) {
+  static_assert(!SR || (std::is_same<P, bf16_t>::value && !MASTER), "stochastic rounding: bf16 parameters, no master");
   const int s = find_seg(t, blockIdx.x);
   const int64_t blk = blockIdx.x - (s ? t.blk_end[s - 1] : 0);
   P* p = reinterpret_cast<P*>(t.ptr[0][s]);
@@ -953,10 +982,20 @@ __global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr
   const int64_t n = t.numel[s];
   const unsigned long long key = mix64(seed ^ mix64((ordinal << 32) | step));
   const uint32_t km = (uint32_t)key, ks = (uint32_t)(key >> 32);
+  const uint32_t kp = SR ? sr_param_key(key) : 0u;
   const float gscale = (gs ? *gs : 1.f) * (maximize ? -1.f : 1.f);
   const float step_size = lr / bc1;
   const int64_t base = blk * kChunk;
   const bool lead = (threadIdx.x & 15) == 0;  // the lane that writes its group's two scales
+  // the parameter's 8 elements from range index i on (16-byte store), and element k alone
+  auto st8_param = [&](int64_t i, const float (&pv)[8]) {
+    if constexpr (SR) st8_sr_bf16(p + i, pv, eoff + i, kp);
+    else Vec8<P>::st(p + i, pv);
+  };
+  auto st_param = [&](int64_t k, float pv) {
+    if constexpr (SR) p[k].x = (uint16_t)sr_bf16(pv, eoff + k, kp);
+    else Elem<P, float>::st(p, k, pv);
+  };
   auto upd = [&](float& pv, float gv, float& mv, float& vv) {
     float gg = gv * gscale;
     if (wd != 0.f) {
@@ -1005,7 +1044,7 @@ __global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr
     for (int it = 0; it < kIters; ++it) {
       const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
       update8(i, 8, pv[it], gv[it], mq[it], sq[it], msc[it], ssc[it]);
-      Vec8<P>::st(p + i, pv[it]);
+      st8_param(i, pv[it]);
       if (MASTER) Vec8<float>::st(mp + i, pv[it]);
       *reinterpret_cast<uint2*>(mqp + i) = make_uint2(mq[it][0], mq[it][1]);
       *reinterpret_cast<uint2*>(sqp + i) = make_uint2(sq[it][0], sq[it][1]);
@@ -1050,7 +1089,7 @@ __global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr
     }
     update8(i, nv, pv, gv, mq, sq, msc, ssc);
     if (VEC && nv == 8) {
-      Vec8<P>::st(p + i, pv);
+      st8_param(i, pv);
       if (MASTER) Vec8<float>::st(mp + i, pv);
       *reinterpret_cast<uint2*>(mqp + i) = make_uint2(mq[0], mq[1]);
       *reinterpret_cast<uint2*>(sqp + i) = make_uint2(sq[0], sq[1]);
@@ -1058,7 +1097,7 @@ __global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         if (j < nv) {
-          Elem<P, float>::st(p, i + j, pv[j]);
+          st_param(i + j, pv[j]);
           if (MASTER) mp[i + j] = pv[j];
           mqp[i + j] = (uint8_t)(mq[j >> 2] >> (8 * (j & 3)));
           sqp[i + j] = (uint8_t)(sq[j >> 2] >> (8 * (j & 3)));
@@ -1078,7 +1117,7 @@ void fused_adam8(const std::vector<at::Tensor>& params, const std::vector<at::Te
                  const std::vector<at::Tensor>& masters, const std::vector<int64_t>& ordinals,
                  const std::vector<int64_t>& group_offsets, double lr, double beta1, double beta2, double eps,
                  double weight_decay, int64_t step, int64_t seed, bool decoupled, bool maximize,
-                 const c10::optional<at::Tensor>& grad_scale, hipStream_t stream) {
+                 const c10::optional<at::Tensor>& grad_scale, bool stochastic_params, hipStream_t stream) {
   const size_t N = params.size();
   TORCH_CHECK(grads.size() == N && m_q.size() == N && m_scale.size() == N && s_q.size() == N && s_scale.size() == N &&
                   ordinals.size() == N && group_offsets.size() == N,
@@ -1089,6 +1128,8 @@ void fused_adam8(const std::vector<at::Tensor>& params, const std::vector<at::Te
   TORCH_CHECK(step >= 1 && step <= (int64_t)UINT32_MAX, "adam8: step must be in [1, 2^32)");
   const auto pt = params[0].scalar_type(), gt = grads[0].scalar_type();
   TORCH_CHECK(pt != at::kDouble && gt != at::kDouble, "fused Adam: fp64 unsupported");
+  TORCH_CHECK(!stochastic_params || (pt == at::kBFloat16 && !has_master),
+              "adam8: stochastic parameter rounding is for bf16 parameters without master weights");
   std::vector<std::array<void*, 9>> ptrs;
   std::vector<int64_t> numels;
   bool vec = true;
@@ -1131,17 +1172,199 @@ void fused_adam8(const std::vector<at::Tensor>& params, const std::vector<at::Te
     case at::kHalf: { using NAME = f16_t; __VA_ARGS__; break; }      \
     default: TORCH_CHECK(false, "fused Adam (8-bit states): unsupported dtype ", st); \
   }
-  XDDP_DISPATCH_ADAM8(pt, P, XDDP_DISPATCH_ADAM8(gt, G, {
+  auto launch = [&](auto k) {
     for_each_table<9>(ptrs, numels, [&](const SegTable<9>& t, int32_t nb) {
-      auto k = vec ? (has_master ? adam8_kernel<P, G, true, true> : adam8_kernel<P, G, true, false>)
-                   : (has_master ? adam8_kernel<P, G, false, true> : adam8_kernel<P, G, false, false>);
       hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t, (float)lr, (float)beta1, (float)beta2,
                          (float)eps, (float)weight_decay, (float)bc1, (float)std::sqrt(bc2), decoupled, maximize, gs,
                          (unsigned long long)seed, (uint32_t)step);
       XDDP_HIP_CHECK(hipGetLastError());
     });
-  }));
+  };
+  if (stochastic_params) {
+    XDDP_DISPATCH_ADAM8(gt, G, launch(vec ? adam8_kernel<bf16_t, G, true, false, true>
+                                          : adam8_kernel<bf16_t, G, false, false, true>));
+  } else {
+    XDDP_DISPATCH_ADAM8(pt, P, XDDP_DISPATCH_ADAM8(gt, G, {
+      launch(vec ? (has_master ? adam8_kernel<P, G, true, true> : adam8_kernel<P, G, true, false>)
+                 : (has_master ? adam8_kernel<P, G, false, true> : adam8_kernel<P, G, false, false>));
+    }));
+  }
 #undef XDDP_DISPATCH_ADAM8
+}
+
+// ------------------------------------------------------------------------------------
+// Stochastically rounded bf16 parameters (no fp32 master): the rounding alone, and fused Adam /
+// AdamW with fp32 moments whose parameter write is sr_bf16. Slots of the latter: {param, grad,
+// exp_avg, exp_avg_sq, parameter ordinal, element offset of the range within its parameter}. The
+// random bits hang on the element's index within its parameter, so any slicing gives the bits of
+// the whole-parameter update. (adam8_kernel<.., SR = true> is the same write with 8-bit moments.)
+// ------------------------------------------------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void sr_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ out,
+                                                           int64_t n, unsigned long long seed,
+                                                           unsigned long long ordinal, uint32_t step, int64_t eoff) {
+  const uint32_t kp = sr_param_key(mix64(seed ^ mix64((ordinal << 32) | step)));
+  const int64_t base = (int64_t)blockIdx.x * kChunk;
+#pragma unroll
+  for (int it = 0; it < kIters; ++it) {
+    const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+    if (VEC && i + 8 <= n) {
+      float v[8];
+      Vec8<float>::ld(x + i, v);
+      st8_sr_bf16(out + i, v, eoff + i, kp);
+    } else {
+      for (int64_t k = i; k < i + 8 && k < n; ++k) out[k].x = (uint16_t)sr_bf16(x[k], eoff + k, kp);
+    }
+  }
+}
+
+void stochastic_round_bf16(const at::Tensor& x, const at::Tensor& out, int64_t seed, int64_t ordinal, int64_t step,
+                           int64_t offset, hipStream_t stream) {
+  TORCH_CHECK(x.is_cuda() && out.is_cuda() && x.scalar_type() == at::kFloat && out.scalar_type() == at::kBFloat16,
+              "stochastic_round_bf16: float32 input and bfloat16 output on the device expected");
+  check_dense_pair(x, out);
+  TORCH_CHECK(seed >= 0 && ordinal >= 0 && ordinal <= (int64_t)UINT32_MAX && step >= 0 &&
+                  step <= (int64_t)UINT32_MAX && offset >= 0,
+              "stochastic_round_bf16: bad seed, ordinal, step or offset");
+  const int64_t n = x.numel();
+  if (n == 0) return;
+  const int64_t nb = (n + kChunk - 1) / kChunk;
+  TORCH_CHECK(nb < (int64_t)(1 << 30), "tensor too large for one launch");
+  const bool vec = aligned16(x.data_ptr()) && aligned16(out.data_ptr());
+  auto k = vec ? sr_bf16_kernel<true> : sr_bf16_kernel<false>;
+  hipLaunchKernelGGL(k, dim3((uint32_t)nb), dim3(kThreads), 0, stream, x.data_ptr<float>(),
+                     reinterpret_cast<bf16_t*>(out.data_ptr()), n, (unsigned long long)seed,
+                     (unsigned long long)ordinal, (uint32_t)step, offset);
+  XDDP_HIP_CHECK(hipGetLastError());
+}
+
+template <typename G, bool VEC>
+__global__ __launch_bounds__(kThreads) void adam_sr_kernel(SegTable<6> t, float lr, float b1, float b2, float eps,
+                                                           float wd, float bc1, float bc2_sqrt, bool decoupled,
+                                                           bool maximize, const float* gs, unsigned long long seed,
+                                                           uint32_t step) {
+  const int s = find_seg(t, blockIdx.x);
+  const int64_t blk = blockIdx.x - (s ? t.blk_end[s - 1] : 0);
+  bf16_t* p = reinterpret_cast<bf16_t*>(t.ptr[0][s]);
+  const G* g = reinterpret_cast<const G*>(t.ptr[1][s]);
+  float* m = reinterpret_cast<float*>(t.ptr[2][s]);
+  float* v = reinterpret_cast<float*>(t.ptr[3][s]);
+  const unsigned long long ordinal = reinterpret_cast<uintptr_t>(t.ptr[4][s]);
+  const int64_t eoff = (int64_t)reinterpret_cast<uintptr_t>(t.ptr[5][s]);
+  const int64_t n = t.numel[s];
+  const uint32_t kp = sr_param_key(mix64(seed ^ mix64((ordinal << 32) | step)));
+  const float gscale = (gs ? *gs : 1.f) * (maximize ? -1.f : 1.f);
+  const float step_size = lr / bc1;
+  const int64_t base = blk * kChunk;
+  auto upd = [&](float& pv, float gv, float& mv, float& vv) {  // adam_kernel's, to the letter
+    float gg = gv * gscale;
+    if (wd != 0.f) {
+      if (decoupled) pv *= (1.f - lr * wd);
+      else gg = fmaf(wd, pv, gg);
+    }
+    mv = fmaf(b1, mv, (1.f - b1) * gg);
+    vv = fmaf(b2, vv, (1.f - b2) * gg * gg);
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    pv = pv - step_size * mv / denom;
+  };
+  if (VEC && base + kChunk <= n) {
+    // whole chunk: every iteration's loads first, then the updates and stores (as adam_kernel)
+    float pv[kIters][8], gv[kIters][8], mv[kIters][8], vv[kIters][8];
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+      Vec8<bf16_t>::ld(p + i, pv[it]);
+      Vec8<G>::ld(g + i, gv[it]);
+      Vec8<float>::ld(m + i, mv[it]);
+      Vec8<float>::ld(v + i, vv[it]);
+    }
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) upd(pv[it][j], gv[it][j], mv[it][j], vv[it][j]);
+      st8_sr_bf16(p + i, pv[it], eoff + i, kp);
+      Vec8<float>::st(m + i, mv[it]);
+      Vec8<float>::st(v + i, vv[it]);
+    }
+    return;
+  }
+#pragma unroll
+  for (int it = 0; it < kIters; ++it) {
+    const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+    if (VEC && i + 8 <= n) {
+      float pv[8], gv[8], mv[8], vv[8];
+      Vec8<bf16_t>::ld(p + i, pv);
+      Vec8<G>::ld(g + i, gv);
+      Vec8<float>::ld(m + i, mv);
+      Vec8<float>::ld(v + i, vv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) upd(pv[j], gv[j], mv[j], vv[j]);
+      st8_sr_bf16(p + i, pv, eoff + i, kp);
+      Vec8<float>::st(m + i, mv);
+      Vec8<float>::st(v + i, vv);
+    } else {
+      for (int64_t k = i; k < i + 8 && k < n; ++k) {
+        float pv = Elem<bf16_t, float>::ld(p, k), gv = Elem<G, float>::ld(g, k), mv = m[k], vv = v[k];
+        upd(pv, gv, mv, vv);
+        p[k].x = (uint16_t)sr_bf16(pv, eoff + k, kp);
+        m[k] = mv;
+        v[k] = vv;
+      }
+    }
+  }
+}
+
+void fused_adam_sr(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                   const std::vector<at::Tensor>& exp_avgs, const std::vector<at::Tensor>& exp_avg_sqs,
+                   const std::vector<int64_t>& ordinals, const std::vector<int64_t>& offsets, double lr, double beta1,
+                   double beta2, double eps, double weight_decay, int64_t step, int64_t seed, bool decoupled,
+                   bool maximize, const c10::optional<at::Tensor>& grad_scale, hipStream_t stream) {
+  const size_t N = params.size();
+  TORCH_CHECK(grads.size() == N && exp_avgs.size() == N && exp_avg_sqs.size() == N && ordinals.size() == N &&
+                  offsets.size() == N,
+              "adam (stochastic rounding): list length mismatch");
+  if (N == 0) return;
+  TORCH_CHECK(step >= 1 && step <= (int64_t)UINT32_MAX && seed >= 0,
+              "adam (stochastic rounding): step must be in [1, 2^32), seed >= 0");
+  const auto gt = grads[0].scalar_type();
+  std::vector<std::array<void*, 6>> ptrs;
+  std::vector<int64_t> numels;
+  bool vec = true;
+  for (size_t i = 0; i < N; ++i) {
+    TORCH_CHECK(params[i].is_cuda() && params[i].scalar_type() == at::kBFloat16 && grads[i].scalar_type() == gt,
+                "adam (stochastic rounding): bf16 device parameters and gradients of one dtype expected");
+    TORCH_CHECK(grads[i].is_cuda() && exp_avgs[i].is_cuda() && exp_avg_sqs[i].is_cuda() &&
+                    exp_avgs[i].scalar_type() == at::kFloat && exp_avg_sqs[i].scalar_type() == at::kFloat,
+                "adam (stochastic rounding): gradients and fp32 states on the device expected");
+    check_dense_pair(params[i], grads[i]);
+    check_dense_pair(params[i], exp_avgs[i]);
+    check_dense_pair(params[i], exp_avg_sqs[i]);
+    TORCH_CHECK(ordinals[i] >= 0 && ordinals[i] <= (int64_t)UINT32_MAX && offsets[i] >= 0,
+                "adam (stochastic rounding): bad parameter ordinal or element offset");
+    ptrs.push_back({params[i].data_ptr(), const_cast<void*>(grads[i].data_ptr()), exp_avgs[i].data_ptr(),
+                    exp_avg_sqs[i].data_ptr(), reinterpret_cast<void*>((uintptr_t)ordinals[i]),
+                    reinterpret_cast<void*>((uintptr_t)offsets[i])});
+    numels.push_back(params[i].numel());
+    for (int q = 0; q < 4; ++q) vec = vec && aligned16(ptrs.back()[q]);
+  }
+  const double bc1 = 1.0 - std::pow(beta1, (double)step);
+  const double bc2 = 1.0 - std::pow(beta2, (double)step);
+  const float* gs = scale_ptr(grad_scale);
+  auto launch = [&](auto k) {
+    for_each_table<6>(ptrs, numels, [&](const SegTable<6>& t, int32_t nb) {
+      hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t, (float)lr, (float)beta1, (float)beta2,
+                         (float)eps, (float)weight_decay, (float)bc1, (float)std::sqrt(bc2), decoupled, maximize, gs,
+                         (unsigned long long)seed, (uint32_t)step);
+      XDDP_HIP_CHECK(hipGetLastError());
+    });
+  };
+  switch (gt) {
+    case at::kFloat: launch(vec ? adam_sr_kernel<float, true> : adam_sr_kernel<float, false>); break;
+    case at::kBFloat16: launch(vec ? adam_sr_kernel<bf16_t, true> : adam_sr_kernel<bf16_t, false>); break;
+    case at::kHalf: launch(vec ? adam_sr_kernel<f16_t, true> : adam_sr_kernel<f16_t, false>); break;
+    default: TORCH_CHECK(false, "fused Adam (stochastic rounding): unsupported gradient dtype ", gt);
+  }
 }
 
 }  // namespace kernels

@@ -1,1 +1,2 @@
-from .fused import FusedAdam, FusedAdamW, FusedSGD, clip_grad_norm_, grad_norm  # noqa: F401
+from .fused import (FusedAdam, FusedAdamW, FusedSGD, clip_grad_norm_, grad_norm,  # noqa: F401
+                    stochastic_round_bf16)

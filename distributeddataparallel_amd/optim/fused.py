@@ -20,7 +20,7 @@ from torch.optim import Optimizer
 
 from .._native import load
 
-__all__ = ["FusedSGD", "FusedAdamW", "FusedAdam", "clip_grad_norm_", "grad_norm"]
+__all__ = ["FusedSGD", "FusedAdamW", "FusedAdam", "clip_grad_norm_", "grad_norm", "stochastic_round_bf16"]
 
 
 def _group_key(p: torch.Tensor, g: torch.Tensor):
@@ -93,6 +93,70 @@ def _quantize_e4m3_sr(x: torch.Tensor, u: torch.Tensor, nonneg: bool):
     else:
         code = code + 128 * torch.signbit(x)
     return code.to(torch.uint8), scale
+
+
+_M32 = 0xFFFFFFFF
+
+
+def _sr_param_key(seed: int, ordinal: int, step: int) -> int:
+    """``kp``, the hash key of the stochastically rounded parameter write: a third stream next to the
+    8-bit moments' ``km`` / ``ks`` (the low / high half of ``key``), the splitmix64 output after it."""
+    key = _mix64(seed ^ _mix64((ordinal << 32) | step))
+    return _mix64(key + 0x9E3779B97F4A7C15) & _M32
+
+
+def _mul32(x: torch.Tensor, c: int) -> torch.Tensor:
+    """``x * c mod 2^32`` for an int64 tensor of 32-bit values, without overflowing int64."""
+    return ((((x * (c >> 16)) & 0xFFFF) << 16) + x * (c & 0xFFFF)) & _M32
+
+
+def _mix32(x: torch.Tensor) -> torch.Tensor:  # the kernels' mix32, on 32-bit values held in int64
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+@torch.no_grad()
+def stochastic_round_bf16(x: torch.Tensor, seed: int, ordinal: int = 0, step: int = 0, offset: int = 0) -> torch.Tensor:
+    """The fp32 tensor ``x`` (dense, taken in memory order) rounded stochastically to bf16.
+
+    Element ``i`` with bits ``u`` gets the upper 16 bits of ``u + r``, ``r`` being 16 random bits: the
+    value is rounded away from zero with probability (discarded 16 bits) / 65536 and truncated
+    otherwise, so the result is ``x`` in expectation, and a value that already is a bf16 is
+    returned unchanged. A finite value never becomes inf (where the sum's exponent would be all ones
+    the upper 16 bits of ``u`` are kept: the largest finite bf16 of that sign), +-inf stay, and NaN
+    gives the quiet NaN ``0x7FC0``. ``r`` is the top half of ``mix32(lo ^ kp ^ hi)`` for the element
+    index ``e = offset + i`` (``lo = e mod 2^32``, ``hi = (e >> 32) * 0x9e3779b9 mod 2^32``) and
+    ``kp`` the parameter-write key of (``seed``, ``ordinal``, ``step``): the third stream of the hash
+    that rounds the 8-bit optimizer states. CUDA tensors run the HIP kernel, CPU tensors the same
+    integer arithmetic in torch; the two agree bit for bit.
+    """
+    if x.dtype != torch.float32:
+        raise TypeError(f"stochastic_round_bf16 expects a float32 tensor, got {x.dtype}")
+    seed, ordinal, step, offset = int(seed), int(ordinal), int(step), int(offset)
+    if not (0 <= seed < 1 << 63 and 0 <= ordinal < 1 << 32 and 0 <= step < 1 << 32 and 0 <= offset < 1 << 62):
+        raise ValueError("stochastic_round_bf16: seed in [0, 2^63), ordinal and step in [0, 2^32), offset >= 0")
+    n = x.numel()
+    src = _flat_range(x, 0, n)  # (raises for a tensor that is not dense)
+    out = torch.empty_like(x, dtype=torch.bfloat16)  # the same strides
+    if n == 0:
+        return out
+    if x.device.type == "cuda":
+        load().stochastic_round_bf16(x, out, seed, ordinal, step, offset)
+        return out
+    u = src.contiguous().view(torch.int32).to(torch.int64) & _M32
+    e = torch.arange(offset, offset + n, dtype=torch.int64)
+    hi = ((e >> 32) * 0x9E3779B9) & _M32
+    r = _mix32((e & _M32) ^ _sr_param_key(seed, ordinal, step) ^ hi) >> 16
+    t = (u + r) & _M32
+    t = torch.where((t & 0x7F800000) == 0x7F800000, u, t)  # no overflow to inf; +-inf keep their bits
+    t = torch.where(((u & 0x7F800000) == 0x7F800000) & ((u & 0x007FFFFF) != 0), torch.full_like(t, 0x7FC00000), t)
+    bits = t >> 16
+    bits = (bits - ((bits & 0x8000) << 1)).to(torch.int16)
+    _flat_range(out, 0, n).copy_(bits.view(torch.bfloat16))
+    return out
 
 
 class _KeepStateDtypes:
@@ -211,26 +275,44 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
     from a ``torch.Generator`` seeded from the same tuple, so it matches the GPU path in
     distribution, not bit for bit. :meth:`decode_states` gives the moments back in fp32.
 
-    With ``state_bits=8`` a step cannot be captured into a HIP graph (``RuntimeError``): the step
-    count is a host value baked into the launch, and a replayed graph would round with the same
-    random bits forever.
+    ``param_rounding="stochastic"`` (default ``"nearest"``) trains bf16 parameters without the fp32
+    master copy: each is updated in fp32 from its bf16 value and written back with
+    :func:`stochastic_round_bf16`, keyed by (``seed``, the parameter's ordinal, its step, the element
+    index), so an update below half a bf16 ulp is applied in expectation where round-to-nearest
+    would drop it every step. No ``master`` state exists (``master_weights=True`` is refused), fp32
+    parameters of the same optimizer are updated as ever, fp16 ones are refused. It combines with
+    either ``state_bits``; the CPU path rounds with the GPU's bits. Replicas that apply the same
+    gradients with the same ``seed`` stay bitwise identical.
+
+    With ``state_bits=8`` or ``param_rounding="stochastic"`` a step cannot be captured into a HIP
+    graph (``RuntimeError``): the step count is a host value baked into the launch, and a replayed
+    graph would round with the same random bits forever.
     """
 
     _decoupled = True
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  maximize: bool = False, master_weights: bool = False, amsgrad: bool = False, state_bits: int = 32,
-                 seed: int = 0):
+                 seed: int = 0, param_rounding: str = "nearest"):
         if amsgrad:
             raise NotImplementedError("amsgrad is not supported by the fused kernel")
         if state_bits not in (8, 32):
             raise ValueError(f"state_bits must be 32 or 8, got {state_bits!r}")
         if not 0 <= int(seed) < 1 << 63:
             raise ValueError("seed must be in [0, 2^63)")
+        if param_rounding not in ("nearest", "stochastic"):
+            raise ValueError(f"param_rounding must be 'nearest' or 'stochastic', got {param_rounding!r}")
+        if param_rounding == "stochastic" and master_weights:
+            raise ValueError("param_rounding='stochastic' replaces the fp32 master weights: "
+                             "master_weights must be False")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, maximize=maximize,
-                        master_weights=master_weights, state_bits=state_bits, seed=int(seed))
+                        master_weights=master_weights, state_bits=state_bits, seed=int(seed),
+                        param_rounding=param_rounding)
         super().__init__(params, defaults)
         self._slice_pos = {}  # 8-bit states: how far this step's pieces of a parameter have come
+        for group in self.param_groups:
+            for p in group["params"]:
+                self._stochastic(p, group)  # (refuses fp16 parameters)
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale: Optional[torch.Tensor] = None):
@@ -241,7 +323,6 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
         self._refuse_capture()
         C = load()
         for group in self.param_groups:
-            b1, b2 = group["betas"]
             if group["state_bits"] == 8:
                 items = [(p, p.grad, 0, p.numel()) for p in group["params"] if p.grad is not None]
                 for p, *_ in items:
@@ -260,7 +341,8 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
                     if group["master_weights"] and p.dtype in (torch.bfloat16, torch.float16):
                         st["master"] = p.detach().float().clone(memory_format=torch.preserve_format)
                 st["step"] += 1
-                key = _group_key(p, p.grad) + (st["step"], "master" in st)
+                sr = self._stochastic(p, group)
+                key = _group_key(p, p.grad) + (st["step"], "master" in st, sr)
                 b = buckets[key]
                 b[0].append(p)
                 b[1].append(p.grad)
@@ -268,13 +350,61 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
                 b[3].append(st["exp_avg_sq"])
                 if "master" in st:
                     b[4].append(st["master"])
-            for (dev, pdt, gdt, step, has_master), (ps, gs, m1, m2, masters, _) in buckets.items():
-                if dev.type == "cuda":
-                    C.fused_adam(ps, gs, m1, m2, masters, group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                                 step, self._decoupled, group["maximize"], grad_scale)
-                else:
-                    self._cpu_step(ps, gs, m1, m2, masters, group, step, grad_scale)
+                if sr:
+                    b[5].append((self._ordinal(p), 0))
+            for key, lists in buckets.items():
+                self._launch32(C, group, key, lists, grad_scale)
         return loss
+
+    def _launch32(self, C, group, key, lists, grad_scale):
+        """One bucket of the 32-bit states: ``lists`` = (params, grads, exp_avgs, exp_avg_sqs, masters,
+        [(ordinal, element offset)] of the stochastically rounded parameters or ranges)."""
+        (dev, pdt, gdt, step, has_master, sr), (ps, gs, m1, m2, masters, keys) = key, lists
+        b1, b2 = group["betas"]
+        if dev.type != "cuda":
+            self._cpu_step(ps, gs, m1, m2, masters, group, step, grad_scale, keys if sr else None)
+        elif sr:
+            C.fused_adam_sr(ps, gs, m1, m2, [o for o, _ in keys], [e for _, e in keys], group["lr"], b1, b2,
+                            group["eps"], group["weight_decay"], step, group["seed"], self._decoupled,
+                            group["maximize"], grad_scale)
+        else:
+            C.fused_adam(ps, gs, m1, m2, masters, group["lr"], b1, b2, group["eps"], group["weight_decay"],
+                         step, self._decoupled, group["maximize"], grad_scale)
+
+    def _stochastic(self, p, group) -> bool:
+        """Whether ``p`` is written with stochastic rounding (bf16 parameters of a
+        ``param_rounding="stochastic"`` group; fp32 ones are exact as they are)."""
+        if group.get("param_rounding", "nearest") != "stochastic" or p.dtype == torch.float32:
+            return False
+        if p.dtype != torch.bfloat16:
+            raise ValueError(f"param_rounding='stochastic' supports bf16 (and fp32) parameters, got {p.dtype}")
+        if group["master_weights"]:
+            raise ValueError("param_rounding='stochastic' replaces the fp32 master weights: "
+                             "master_weights must be False")
+        return True
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """As the base class; ``param_rounding`` stays this optimizer's. A state saved with fp32 master
+        weights loads into a ``param_rounding="stochastic"`` optimizer: every such parameter becomes
+        ``stochastic_round_bf16(master)`` keyed at the saved step, and its master is dropped. A state
+        saved with stochastic rounding has no masters to give a ``"nearest"`` optimizer: ``ValueError``."""
+        own = [g["param_rounding"] for g in self.param_groups]
+        saved = [g.get("param_rounding", "nearest") for g in state_dict["param_groups"]]
+        if any(s == "stochastic" and o != "stochastic" for o, s in zip(own, saved)):
+            raise ValueError("this state was saved with param_rounding='stochastic': it holds no fp32 master weights, "
+                             "and its bf16 parameters carry the rounding. Load it into an optimizer constructed "
+                             "with param_rounding='stochastic'")
+        super().load_state_dict(state_dict)
+        for group, rounding in zip(self.param_groups, own):
+            group["param_rounding"] = rounding
+            if rounding != "stochastic":
+                continue
+            group["master_weights"] = False
+            for p in group["params"]:
+                master = self.state[p].pop("master", None) if p in self.state else None
+                if master is not None and self._stochastic(p, group):
+                    p.copy_(stochastic_round_bf16(master, group["seed"], self._ordinal(p), self.state[p]["step"]))
 
     def _group_index(self, p):
         if not hasattr(self, "_group_of"):
@@ -287,11 +417,17 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
         return self._ordinal_of[id(p)]
 
     def _refuse_capture(self):
-        if (torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
-                and any(g["state_bits"] == 8 for g in self.param_groups)):
+        if not (torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()):
+            return
+        if any(g["state_bits"] == 8 for g in self.param_groups):
             raise RuntimeError("FusedAdamW(state_bits=8) cannot be captured into a HIP graph: the step count that "
                                "seeds the stochastic rounding is a host value, so a replay would reuse one set of "
                                "random bits; step outside the capture, or use state_bits=32")
+        if any(g.get("param_rounding") == "stochastic" for g in self.param_groups):
+            raise RuntimeError("FusedAdamW(param_rounding='stochastic') cannot be captured into a HIP graph: the "
+                               "step count that seeds the stochastic rounding is a host value, so a replay would "
+                               "reuse one set of random bits; step outside the capture, or use "
+                               "param_rounding='nearest'")
 
     def _init_state(self, p, group):
         st = self.state[p]
@@ -355,7 +491,6 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
                 per_group[gi].append((p, g, lo, hi))
         for gi, items in per_group.items():
             group = self.param_groups[gi]
-            b1, b2 = group["betas"]
             if group["state_bits"] == 8:
                 ranges = []
                 for p, g, lo, hi in items:
@@ -376,7 +511,8 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
                 st = self._init_state(p, group)
                 if st["step"] == 0:
                     raise RuntimeError("step_slices before advance() for this step")
-                b = buckets[_group_key(p, g) + (st["step"], "master" in st)]
+                sr = self._stochastic(p, group)
+                b = buckets[_group_key(p, g) + (st["step"], "master" in st, sr)]
                 whole = lo == 0 and hi == p.numel()
                 cut = (lambda t: t) if whole else (lambda t: _flat_range(t, lo, hi))
                 b[0].append(cut(p))
@@ -385,12 +521,10 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
                 b[3].append(cut(st["exp_avg_sq"]))
                 if "master" in st:
                     b[4].append(cut(st["master"]))
-            for (dev, pdt, gdt, step, has_master), (ps, gs, m1, m2, masters, _) in buckets.items():
-                if dev.type == "cuda":
-                    C.fused_adam(ps, gs, m1, m2, masters, group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                                 step, self._decoupled, group["maximize"], None)
-                else:
-                    self._cpu_step(ps, gs, m1, m2, masters, group, step, None)
+                if sr:
+                    b[5].append((self._ordinal(p), lo))
+            for key, lists in buckets.items():
+                self._launch32(C, group, key, lists, None)
 
     def _step8(self, group, ranges, grad_scale):
         """8-bit states: update ``ranges`` = ``[(param, grad, lo, hi)]``, ``lo`` a multiple of 128 and
@@ -401,7 +535,7 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
             st = self.state[p]
             if g.stride() != p.stride() and not (g.is_contiguous() and p.is_contiguous()):
                 raise ValueError("state_bits=8 needs the gradient in the parameter's memory order")
-            b = buckets[_group_key(p, g) + (st["step"], "master" in st)]
+            b = buckets[_group_key(p, g) + (st["step"], "master" in st, self._stochastic(p, group))]
             glo, ghi = lo // _QGROUP, (hi + _QGROUP - 1) // _QGROUP
             b[0].append(_flat_range(p, lo, hi))
             b[1].append(_flat_range(g, lo, hi))
@@ -413,17 +547,18 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
                 b[6].append(_flat_range(st["master"], lo, hi))
             b[7].append(self._ordinal(p))
             b[8].append((glo, p.numel()))
-        for (dev, pdt, gdt, step, has_master), (ps, gs, mq, ms, sq, ss, masters, ords, offs) in buckets.items():
+        for (dev, pdt, gdt, step, has_master, sr), (ps, gs, mq, ms, sq, ss, masters, ords, offs) in buckets.items():
             if dev.type == "cuda":
                 load().fused_adam8(ps, gs, mq, ms, sq, ss, masters, ords, [o for o, _ in offs], group["lr"], b1, b2,
                                    group["eps"], group["weight_decay"], step, group["seed"], self._decoupled,
-                                   group["maximize"], grad_scale)
+                                   group["maximize"], grad_scale, stochastic_params=sr)
                 continue
             for i, (p, g) in enumerate(zip(ps, gs)):
                 n, (glo, numel) = p.numel(), offs[i]
                 m = _dequantize_e4m3(mq[i], ms[i])
                 v = _dequantize_e4m3(sq[i], ss[i]).square_()
-                self._cpu_step([p], [g], [m], [v], masters[i:i + 1], group, step, grad_scale)
+                self._cpu_step([p], [g], [m], [v], masters[i:i + 1], group, step, grad_scale,
+                               [(ords[i], glo * _QGROUP)] if sr else None)
                 for moment, x, codes, scales in ((0, m, mq[i], ms[i]), (1, v.sqrt_(), sq[i], ss[i])):
                     gen = torch.Generator().manual_seed(
                         _mix64(group["seed"] ^ _mix64((ords[i] << 32 | step) * 2 + moment)) >> 1)
@@ -448,7 +583,9 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
             out.append(t)
         return tuple(out)
 
-    def _cpu_step(self, ps, gs, m1, m2, masters, group, step, grad_scale):
+    def _cpu_step(self, ps, gs, m1, m2, masters, group, step, grad_scale, sr_keys=None):
+        """``sr_keys``: per parameter (or range) its (ordinal, element offset within the parameter) where
+        the write is stochastically rounded: the GPU's rounding and bits, given the same fp32 value."""
         b1, b2 = group["betas"]
         lr, eps, wd = group["lr"], group["eps"], group["weight_decay"]
         bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
@@ -468,6 +605,8 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
             w = w - (lr / bc1) * m1[i] / denom
             if masters:
                 masters[i].copy_(w)
+            if sr_keys is not None:
+                w = stochastic_round_bf16(w, group["seed"], sr_keys[i][0], step, sr_keys[i][1])
             p.copy_(w)
 
 
@@ -477,8 +616,9 @@ class FusedAdam(FusedAdamW):
     _decoupled = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, maximize=False,
-                 master_weights=False, amsgrad=False, state_bits=32, seed=0):
-        super().__init__(params, lr, betas, eps, weight_decay, maximize, master_weights, amsgrad, state_bits, seed)
+                 master_weights=False, amsgrad=False, state_bits=32, seed=0, param_rounding="nearest"):
+        super().__init__(params, lr, betas, eps, weight_decay, maximize, master_weights, amsgrad, state_bits, seed,
+                         param_rounding)
 
 
 def grad_norm(parameters: Iterable[torch.Tensor], max_norm: float = 0.0) -> torch.Tensor:

@@ -38,7 +38,13 @@ __device__ __forceinline__ uint32_t pack_f16x2(float a, float b) {
   f16x2 r = __builtin_convertvector(v, f16x2);
   return __builtin_bit_cast(uint32_t, r);
 }
-__device__ __forceinline__ uint16_t f32_to_f16(float a) { return __builtin_bit_cast(uint16_t, (_Float16)a); }
+// Rounds the fp32 value it is given, once. The empty asm keeps the conversion from being contracted with
+// the multiply or FMA that produced `a` into one mixed-precision instruction, which rounds the exact
+// product straight to fp16 (not what the packed vector stores do) and turns -0 * 1 into +0.
+__device__ __forceinline__ uint16_t f32_to_f16(float a) {
+  asm("" : "+v"(a));
+  return __builtin_bit_cast(uint16_t, (_Float16)a);
+}
 
 // ---- exact (erf-form) GELU at a few VALU ops ---------------------------------------
 // erf(z) = 1 - t (a1 + t (a2 + t (a3 + t (a4 + t a5)))) e^{-z^2}, t = 1 / (1 + p z), z >= 0

@@ -28,12 +28,14 @@ void mt_pack(const std::vector<at::Tensor>& src, const at::Tensor& flat, const s
 void mt_unpack(const at::Tensor& flat, const std::vector<int64_t>& offsets, const std::vector<at::Tensor>& dst,
                double scale, hipStream_t stream);
 
-// Sum of squares of all elements of all tensors, in fp32, written to out[0] (device scalar).
-// If max_norm > 0, out[1] = min(1, max_norm / (sqrt(out[0]) + 1e-6)) (clip coefficient), and
-// out[0] holds the total L2 norm. `out` must be a float32 tensor with >= 2 elements.
+// out[0] = total L2 norm of all elements of all tensors (device scalar), summed in fp32 (fp64 tensors:
+// in fp64, so squares beyond fp32's range do not overflow). out[1] = the clip coefficient
+// min(1, max_norm / (out[0] + 1e-6)) if max_norm > 0, else 1. `out` must be a float32 tensor with
+// >= 2 elements.
 void mt_l2norm(const std::vector<at::Tensor>& tensors, const at::Tensor& out, double max_norm, hipStream_t stream);
 
-// out[0] (int32) becomes 1 if any element of any tensor is NaN/Inf; 0 otherwise (zeroed here).
+// out[0] (int32) becomes 1 if any element of any tensor is NaN/Inf; 0 otherwise (zeroed here). fp64
+// tensors are tested as fp64: a finite value beyond fp32's range is finite.
 void mt_nonfinite(const std::vector<at::Tensor>& tensors, const at::Tensor& out, hipStream_t stream);
 
 // Replica checksum of a list of dense device tensors (any dtypes): float64 [3] = (fp64 sum of the

@@ -266,27 +266,40 @@ void mt_unpack(const at::Tensor& flat, const std::vector<int64_t>& offsets, cons
 // ------------------------------------------------------------------------------------
 // L2 norm (deterministic two-pass: per-block partials, then one block folds them)
 // ------------------------------------------------------------------------------------
+// The type a tensor's elements are read and reduced in: fp32, except fp64 tensors, whose values
+// (and squares) may lie outside fp32's range.
+template <typename T>
+struct Compute {
+  using type = float;
+};
+template <>
+struct Compute<double> {
+  using type = double;
+};
+
 template <typename T, bool VEC>
-__global__ __launch_bounds__(kThreads) void sumsq_kernel(SegTable<1> t, float* partials, int32_t part_off) {
-  __shared__ float scratch[kThreads / 64];
+__global__ __launch_bounds__(kThreads) void sumsq_kernel(SegTable<1> t, typename Compute<T>::type* partials,
+                                                         int32_t part_off) {
+  using A = typename Compute<T>::type;
+  __shared__ A scratch[kThreads / 64];
   const int s = find_seg(t, blockIdx.x);
   const int64_t blk = blockIdx.x - (s ? t.blk_end[s - 1] : 0);
   const T* x = reinterpret_cast<const T*>(t.ptr[0][s]);
   const int64_t n = t.numel[s];
   const int64_t base = blk * kChunk;
-  float acc = 0.f;
+  A acc = 0;
 #pragma unroll
   for (int it = 0; it < kIters; ++it) {
     const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
     if (VEC && i + 8 <= n) {
-      float v[8];
+      A v[8];
       Vec8<T>::ld(x + i, v);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) acc = fmaf(v[j], v[j], acc);
+      for (int j = 0; j < 8; ++j) acc = fma(v[j], v[j], acc);
     } else {
       for (int64_t k = i; k < i + 8 && k < n; ++k) {
-        float v = Elem<T, float>::ld(x, k);
-        acc = fmaf(v, v, acc);
+        A v = Elem<T, A>::ld(x, k);
+        acc = fma(v, v, acc);
       }
     }
   }
@@ -294,16 +307,18 @@ __global__ __launch_bounds__(kThreads) void sumsq_kernel(SegTable<1> t, float* p
   if (threadIdx.x == 0) partials[part_off + blockIdx.x] = acc;
 }
 
-__global__ __launch_bounds__(1024) void norm_finalize_kernel(const float* partials, int64_t n, float* out,
+// out[1] is always written: 1 when there is nothing to clip to (max_norm <= 0)
+template <typename A>
+__global__ __launch_bounds__(1024) void norm_finalize_kernel(const A* partials, int64_t n, float* out,
                                                              float max_norm) {
-  __shared__ float scratch[1024 / 64];
-  float acc = 0.f;
+  __shared__ A scratch[1024 / 64];
+  A acc = 0;
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x) acc += partials[i];
   acc = dev::block_sum(acc, scratch);
   if (threadIdx.x == 0) {
-    const float norm = sqrtf(acc);
+    const float norm = (float)sqrt(acc);
     out[0] = norm;
-    if (max_norm > 0.f) out[1] = fminf(1.f, max_norm / (norm + 1e-6f));
+    out[1] = max_norm > 0.f ? fminf(1.f, max_norm / (norm + 1e-6f)) : 1.f;
   }
 }
 
@@ -311,7 +326,7 @@ void mt_l2norm(const std::vector<at::Tensor>& tensors, const at::Tensor& out, do
   TORCH_CHECK(out.scalar_type() == at::kFloat && out.numel() >= 2 && out.is_cuda(), "out must be float32[>=2] on device");
   if (tensors.empty()) {
     out.zero_();
-    if (max_norm > 0) out.narrow(0, 1, 1).fill_(1.0);
+    out.narrow(0, 1, 1).fill_(1.0);
     return;
   }
   const auto st = tensors[0].scalar_type();
@@ -327,21 +342,23 @@ void mt_l2norm(const std::vector<at::Tensor>& tensors, const at::Tensor& out, do
     total_blocks += (x.numel() + kChunk - 1) / kChunk;
     vec = vec && aligned16(x.data_ptr());
   }
-  auto partials = at::empty({std::max<int64_t>(total_blocks, 1)}, out.options());
+  auto partials = at::empty({std::max<int64_t>(total_blocks, 1)}, out.options().dtype(st == at::kDouble ? at::kDouble : at::kFloat));
   int32_t off = 0;
   XDDP_DISPATCH_FLOAT(st, T, {
+    using A = typename Compute<T>::type;
+    A* part = partials.data_ptr<A>();
     for_each_table<1>(ptrs, numels, [&](const SegTable<1>& t, int32_t nb) {
       if (vec)
-        hipLaunchKernelGGL((sumsq_kernel<T, true>), dim3(nb), dim3(kThreads), 0, stream, t, partials.data_ptr<float>(), off);
+        hipLaunchKernelGGL((sumsq_kernel<T, true>), dim3(nb), dim3(kThreads), 0, stream, t, part, off);
       else
-        hipLaunchKernelGGL((sumsq_kernel<T, false>), dim3(nb), dim3(kThreads), 0, stream, t, partials.data_ptr<float>(), off);
+        hipLaunchKernelGGL((sumsq_kernel<T, false>), dim3(nb), dim3(kThreads), 0, stream, t, part, off);
       XDDP_HIP_CHECK(hipGetLastError());
       off += nb;
     });
+    hipLaunchKernelGGL(norm_finalize_kernel<A>, dim3(1), dim3(1024), 0, stream, part, (int64_t)off,
+                       out.data_ptr<float>(), (float)max_norm);
+    XDDP_HIP_CHECK(hipGetLastError());
   });
-  hipLaunchKernelGGL(norm_finalize_kernel, dim3(1), dim3(1024), 0, stream, partials.data_ptr<float>(), (int64_t)off,
-                     out.data_ptr<float>(), (float)max_norm);
-  XDDP_HIP_CHECK(hipGetLastError());
 }
 
 // ------------------------------------------------------------------------------------
@@ -355,7 +372,7 @@ __global__ __launch_bounds__(kThreads) void nonfinite_kernel(SegTable<1> t, int*
   const int64_t n = t.numel[s];
   bool bad = false;
   for (int64_t k = blk * kChunk + threadIdx.x; k < std::min(n, (blk + 1) * kChunk); k += kThreads) {
-    float v = Elem<T, float>::ld(x, k);
+    const typename Compute<T>::type v = Elem<T, typename Compute<T>::type>::ld(x, k);  // fp64 tested as fp64
     bad |= !isfinite(v);
   }
   if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
@@ -713,7 +730,8 @@ void fused_sgd(const std::vector<at::Tensor>& params, const std::vector<at::Tens
 // Fused Adam / AdamW: slots {param, grad, exp_avg, exp_avg_sq, master}
 // ------------------------------------------------------------------------------------
 template <typename P, typename G, bool VEC, bool MASTER>
-__global__ __launch_bounds__(kThreads) void adam_kernel(SegTable<5> t, float lr, float b1, float b2, float eps,
+__global__ __launch_bounds__(kThreads) void adam_kernel(SegTable<5> t, float lr, float b1, float b2, float omb1,
+    float omb2, float eps,
                                                         float wd, float bc1, float bc2_sqrt, bool decoupled,
                                                         bool maximize, const float* gs) {
   const int s = find_seg(t, blockIdx.x);
@@ -727,14 +745,16 @@ __global__ __launch_bounds__(kThreads) void adam_kernel(SegTable<5> t, float lr,
   const float gscale = (gs ? *gs : 1.f) * (maximize ? -1.f : 1.f);
   const float step_size = lr / bc1;
   const int64_t base = blk * kChunk;
+  // omb1 / omb2 are 1 - beta1 / 1 - beta2 formed in fp64 on the host: 1.f - b2 from the rounded b2 = 0.999f
+  // is 1.3e-5 off, which exp_avg_sq and the denominator would carry.
   auto upd = [&](float& pv, float gv, float& mv, float& vv) {
     float gg = gv * gscale;
     if (wd != 0.f) {
       if (decoupled) pv *= (1.f - lr * wd);
       else gg = fmaf(wd, pv, gg);
     }
-    mv = fmaf(b1, mv, (1.f - b1) * gg);
-    vv = fmaf(b2, vv, (1.f - b2) * gg * gg);
+    mv = fmaf(b1, mv, omb1 * gg);
+    vv = fmaf(b2, vv, omb2 * gg * gg);
     const float denom = sqrtf(vv) / bc2_sqrt + eps;
     pv = pv - step_size * mv / denom;
   };
@@ -834,7 +854,7 @@ void fused_adam(const std::vector<at::Tensor>& params, const std::vector<at::Ten
       auto k = vec ? (has_master ? adam_kernel<P, G, true, true> : adam_kernel<P, G, true, false>)
                    : (has_master ? adam_kernel<P, G, false, true> : adam_kernel<P, G, false, false>);
       hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t, (float)lr, (float)beta1, (float)beta2,
-                         (float)eps, (float)weight_decay, (float)bc1, (float)std::sqrt(bc2), decoupled, maximize, gs);
+                         (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)bc1, (float)std::sqrt(bc2), decoupled, maximize, gs);
       XDDP_HIP_CHECK(hipGetLastError());
     });
   }));
@@ -963,7 +983,8 @@ __device__ __forceinline__ void adam8_quantize(const float (&m)[8], const float 
 
 // SR: bf16 parameters without a master, written with sr_bf16 (keyed like the moments, third stream).
 template <typename P, typename G, bool VEC, bool MASTER, bool SR = false>
-__global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr, float b1, float b2, float eps,
+__global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr, float b1, float b2, float omb1,
+    float omb2, float eps,
                                                          float wd, float bc1, float bc2_sqrt, bool decoupled,
                                                          bool maximize, const float* gs, unsigned long long seed,
                                                          uint32_t step) {
@@ -1002,8 +1023,8 @@ __global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr
       if (decoupled) pv *= (1.f - lr * wd);
       else gg = fmaf(wd, pv, gg);
     }
-    mv = fmaf(b1, mv, (1.f - b1) * gg);
-    vv = fmaf(b2, vv, (1.f - b2) * gg * gg);
+    mv = fmaf(b1, mv, omb1 * gg);
+    vv = fmaf(b2, vv, omb2 * gg * gg);
     const float denom = sqrtf(vv) / bc2_sqrt + eps;
     pv = pv - step_size * mv / denom;
   };
@@ -1175,7 +1196,7 @@ void fused_adam8(const std::vector<at::Tensor>& params, const std::vector<at::Te
   auto launch = [&](auto k) {
     for_each_table<9>(ptrs, numels, [&](const SegTable<9>& t, int32_t nb) {
       hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t, (float)lr, (float)beta1, (float)beta2,
-                         (float)eps, (float)weight_decay, (float)bc1, (float)std::sqrt(bc2), decoupled, maximize, gs,
+                         (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)bc1, (float)std::sqrt(bc2), decoupled, maximize, gs,
                          (unsigned long long)seed, (uint32_t)step);
       XDDP_HIP_CHECK(hipGetLastError());
     });
@@ -1239,7 +1260,8 @@ void stochastic_round_bf16(const at::Tensor& x, const at::Tensor& out, int64_t s
 }
 
 template <typename G, bool VEC>
-__global__ __launch_bounds__(kThreads) void adam_sr_kernel(SegTable<6> t, float lr, float b1, float b2, float eps,
+__global__ __launch_bounds__(kThreads) void adam_sr_kernel(SegTable<6> t, float lr, float b1, float b2, float omb1,
+    float omb2, float eps,
                                                            float wd, float bc1, float bc2_sqrt, bool decoupled,
                                                            bool maximize, const float* gs, unsigned long long seed,
                                                            uint32_t step) {
@@ -1262,8 +1284,8 @@ __global__ __launch_bounds__(kThreads) void adam_sr_kernel(SegTable<6> t, float 
       if (decoupled) pv *= (1.f - lr * wd);
       else gg = fmaf(wd, pv, gg);
     }
-    mv = fmaf(b1, mv, (1.f - b1) * gg);
-    vv = fmaf(b2, vv, (1.f - b2) * gg * gg);
+    mv = fmaf(b1, mv, omb1 * gg);
+    vv = fmaf(b2, vv, omb2 * gg * gg);
     const float denom = sqrtf(vv) / bc2_sqrt + eps;
     pv = pv - step_size * mv / denom;
   };
@@ -1354,7 +1376,7 @@ void fused_adam_sr(const std::vector<at::Tensor>& params, const std::vector<at::
   auto launch = [&](auto k) {
     for_each_table<6>(ptrs, numels, [&](const SegTable<6>& t, int32_t nb) {
       hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t, (float)lr, (float)beta1, (float)beta2,
-                         (float)eps, (float)weight_decay, (float)bc1, (float)std::sqrt(bc2), decoupled, maximize, gs,
+                         (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)bc1, (float)std::sqrt(bc2), decoupled, maximize, gs,
                          (unsigned long long)seed, (uint32_t)step);
       XDDP_HIP_CHECK(hipGetLastError());
     });

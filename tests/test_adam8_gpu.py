@@ -169,7 +169,7 @@ def test_stochastic_rounding_is_unbiased():
     p.grad = g
     opt.step()
     st = opt.state[p]
-    one_minus_b1 = torch.tensor(1.0, dtype=torch.float32) - torch.tensor(0.9, dtype=torch.float32)
+    one_minus_b1 = torch.tensor(1.0 - 0.9, dtype=torch.float32)  # formed in fp64 on the host, then rounded
     m_exact = (one_minus_b1 * g.cpu())  # fmaf(b1, 0, (1 - b1) g), fp32
     scale = m_exact[0] / 448.0
     assert torch.equal(st["exp_avg_scale"].cpu(), scale.expand(n // 128))

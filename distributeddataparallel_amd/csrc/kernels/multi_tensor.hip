@@ -48,6 +48,17 @@ __device__ __forceinline__ int find_seg(const SegTable<NPTR>& t, int b) {
   return lo;
 }
 
+// What a block of a list kernel works on: segment `s`, its element count and the block's first element
+struct Chunk {
+  int s;
+  int64_t n, base;
+};
+template <int NPTR>
+__device__ __forceinline__ Chunk block_chunk(const SegTable<NPTR>& t) {
+  const int s = find_seg(t, blockIdx.x);
+  const int64_t blk = blockIdx.x - (s ? t.blk_end[s - 1] : 0);
+  return {s, t.numel[s], blk * kChunk};
+}
 // Builds segment tables and launches `launch(table, nblocks)` whenever one fills.
 template <int NPTR, typename F>
 static void for_each_table(const std::vector<std::array<void*, NPTR>>& ptrs, const std::vector<int64_t>& numels,
@@ -129,13 +140,21 @@ struct DevType<at::Half> {
   using type = f16_t;
 };
 
+#define XDDP_DISPATCH_CASES_F32_BF16_F16(NAME, ...)                  \
+    case at::kFloat: { using NAME = float; __VA_ARGS__; break; }     \
+    case at::kBFloat16: { using NAME = bf16_t; __VA_ARGS__; break; } \
+    case at::kHalf: { using NAME = f16_t; __VA_ARGS__; break; }
 #define XDDP_DISPATCH_FLOAT(st, NAME, ...)                                     \
   switch (st) {                                                                \
-    case at::kFloat: { using NAME = float; __VA_ARGS__; break; }               \
-    case at::kBFloat16: { using NAME = bf16_t; __VA_ARGS__; break; }           \
-    case at::kHalf: { using NAME = f16_t; __VA_ARGS__; break; }                \
+    XDDP_DISPATCH_CASES_F32_BF16_F16(NAME, __VA_ARGS__)                        \
     case at::kDouble: { using NAME = double; __VA_ARGS__; break; }             \
     default: TORCH_CHECK(false, "xddp multi-tensor: unsupported dtype ", st);  \
+  }
+// for kernels without an fp64 form; `what` is the error message up to the dtype
+#define XDDP_DISPATCH_FLOAT_NO_F64(st, NAME, what, ...)  \
+  switch (st) {                                          \
+    XDDP_DISPATCH_CASES_F32_BF16_F16(NAME, __VA_ARGS__)  \
+    default: TORCH_CHECK(false, what, st);               \
   }
 
 // ------------------------------------------------------------------------------------
@@ -545,102 +564,89 @@ at::Tensor mt_checksum(const std::vector<at::Tensor>& tensors, hipStream_t strea
 }
 
 // ------------------------------------------------------------------------------------
-// Fused SGD: slots {param, grad, momentum_buf}
+// Fused optimizers. Every kernel takes its hyperparameters in one by-value struct, and every
+// variant of an optimizer runs one update function.
 // ------------------------------------------------------------------------------------
-template <typename P, typename G, bool VEC, bool MOM>
-__global__ __launch_bounds__(kThreads) void sgd_kernel(SegTable<3> t, float lr, float momentum, float dampening,
-                                                       float wd, bool nesterov, bool maximize, bool first,
-                                                       const float* gs) {
-  const int s = find_seg(t, blockIdx.x);
-  const int64_t blk = blockIdx.x - (s ? t.blk_end[s - 1] : 0);
-  P* p = reinterpret_cast<P*>(t.ptr[0][s]);
-  const G* g = reinterpret_cast<const G*>(t.ptr[1][s]);
-  float* buf = reinterpret_cast<float*>(t.ptr[2][s]);
-  const int64_t n = t.numel[s];
-  const float gscale = (gs ? *gs : 1.f) * (maximize ? -1.f : 1.f);
-  const int64_t base = blk * kChunk;
-  auto upd = [&](float& pv, float gv, float& bv) {
+// Launches `kernel(table, args)` over the list, one launch per segment table.
+template <int NPTR, typename K, typename A>
+static void launch_list(K kernel, const std::vector<std::array<void*, NPTR>>& ptrs, const std::vector<int64_t>& numels,
+                        const A& args, hipStream_t stream) {
+  for_each_table<NPTR>(ptrs, numels, [&](const SegTable<NPTR>& t, int32_t nb) {
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(kThreads), 0, stream, t, args);
+    XDDP_HIP_CHECK(hipGetLastError());
+  });
+}
+
+// ------------------------------------------------------------------------------------
+// Fused SGD: slots {param, grad, momentum_buf}, or with master weights {fp32 master, grad, fp32
+// momentum, low-precision model param}
+// ------------------------------------------------------------------------------------
+struct SgdArgs {
+  float lr, momentum, dampening, wd;
+  bool nesterov, maximize, first;
+  const float* gs;
+};
+
+template <bool MOM>
+struct SgdUpdate {
+  const SgdArgs& a;
+  const float gscale;
+  __device__ __forceinline__ explicit SgdUpdate(const SgdArgs& a_)
+      : a(a_), gscale((a_.gs ? *a_.gs : 1.f) * (a_.maximize ? -1.f : 1.f)) {}
+  __device__ __forceinline__ void operator()(float& pv, float gv, float& bv) const {
     float d = gv * gscale;
-    if (wd != 0.f) d = fmaf(wd, pv, d);
+    if (a.wd != 0.f) d = fmaf(a.wd, pv, d);
     if (MOM) {
-      bv = first ? d : fmaf(momentum, bv, (1.f - dampening) * d);
-      d = nesterov ? fmaf(momentum, bv, d) : bv;
+      bv = a.first ? d : fmaf(a.momentum, bv, (1.f - a.dampening) * d);
+      d = a.nesterov ? fmaf(a.momentum, bv, d) : bv;
     }
-    pv = fmaf(-lr, d, pv);
-  };
+    pv = fmaf(-a.lr, d, pv);
+  }
+};
+
+// MASTER: the update reads and writes the fp32 master, and the updated master is rounded into the
+// model's param (of type P) in the same pass (no second launch that re-reads the masters).
+template <typename P, typename G, bool VEC, bool MOM, bool MASTER>
+__global__ __launch_bounds__(kThreads) void sgd_kernel(SegTable<MASTER ? 4 : 3> t, SgdArgs a) {
+  using W = std::conditional_t<MASTER, float, P>;  // what the update reads and writes
+  const Chunk c = block_chunk(t);
+  W* p = reinterpret_cast<W*>(t.ptr[0][c.s]);
+  const G* g = reinterpret_cast<const G*>(t.ptr[1][c.s]);
+  float* buf = reinterpret_cast<float*>(t.ptr[2][c.s]);
+  P* q = nullptr;
+  if constexpr (MASTER) q = reinterpret_cast<P*>(t.ptr[3][c.s]);
+  const int64_t n = c.n;
+  const SgdUpdate<MOM> upd(a);
 #pragma unroll
   for (int it = 0; it < kIters; ++it) {
-    const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+    const int64_t i = c.base + ((int64_t)it * kThreads + threadIdx.x) * 8;
     if (VEC && i + 8 <= n) {
       float pv[8], gv[8], bv[8];
-      Vec8<P>::ld(p + i, pv);
+      Vec8<W>::ld(p + i, pv);
       Vec8<G>::ld(g + i, gv);
-      if (MOM && !first) Vec8<float>::ld(buf + i, bv);
+      if (MOM && !a.first) Vec8<float>::ld(buf + i, bv);
 #pragma unroll
       for (int j = 0; j < 8; ++j) upd(pv[j], gv[j], bv[j]);
-      Vec8<P>::st(p + i, pv);
+      Vec8<W>::st(p + i, pv);
       if (MOM) Vec8<float>::st(buf + i, bv);
+      if (MASTER) Vec8<P>::st(q + i, pv);
     } else {
       for (int64_t k = i; k < i + 8 && k < n; ++k) {
-        float pv = Elem<P, float>::ld(p, k), gv = Elem<G, float>::ld(g, k), bv = 0.f;
-        if (MOM && !first) bv = buf[k];
+        float pv = Elem<W, float>::ld(p, k), gv = Elem<G, float>::ld(g, k), bv = 0.f;
+        if (MOM && !a.first) bv = buf[k];
         upd(pv, gv, bv);
-        Elem<P, float>::st(p, k, pv);
+        Elem<W, float>::st(p, k, pv);
         if (MOM) buf[k] = bv;
+        if (MASTER) Elem<P, float>::st(q, k, pv);
       }
     }
   }
 }
 
-// Master-weight SGD: slots {fp32 master, grad, fp32 momentum, low-precision model param}. The
-// updated master is rounded into the model's param in the same pass (no second launch that
-// re-reads the masters).
-template <typename G, typename Mdl, bool VEC, bool MOM>
-__global__ __launch_bounds__(kThreads) void sgd_master_kernel(SegTable<4> t, float lr, float momentum,
-                                                              float dampening, float wd, bool nesterov,
-                                                              bool maximize, bool first, const float* gs) {
-  const int s = find_seg(t, blockIdx.x);
-  const int64_t blk = blockIdx.x - (s ? t.blk_end[s - 1] : 0);
-  float* p = reinterpret_cast<float*>(t.ptr[0][s]);
-  const G* g = reinterpret_cast<const G*>(t.ptr[1][s]);
-  float* buf = reinterpret_cast<float*>(t.ptr[2][s]);
-  Mdl* q = reinterpret_cast<Mdl*>(t.ptr[3][s]);
-  const int64_t n = t.numel[s];
-  const float gscale = (gs ? *gs : 1.f) * (maximize ? -1.f : 1.f);
-  const int64_t base = blk * kChunk;
-  auto upd = [&](float& pv, float gv, float& bv) {
-    float d = gv * gscale;
-    if (wd != 0.f) d = fmaf(wd, pv, d);
-    if (MOM) {
-      bv = first ? d : fmaf(momentum, bv, (1.f - dampening) * d);
-      d = nesterov ? fmaf(momentum, bv, d) : bv;
-    }
-    pv = fmaf(-lr, d, pv);
-  };
-#pragma unroll
-  for (int it = 0; it < kIters; ++it) {
-    const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
-    if (VEC && i + 8 <= n) {
-      float pv[8], gv[8], bv[8];
-      Vec8<float>::ld(p + i, pv);
-      Vec8<G>::ld(g + i, gv);
-      if (MOM && !first) Vec8<float>::ld(buf + i, bv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) upd(pv[j], gv[j], bv[j]);
-      Vec8<float>::st(p + i, pv);
-      if (MOM) Vec8<float>::st(buf + i, bv);
-      Vec8<Mdl>::st(q + i, pv);
-    } else {
-      for (int64_t k = i; k < i + 8 && k < n; ++k) {
-        float pv = p[k], gv = Elem<G, float>::ld(g, k), bv = 0.f;
-        if (MOM && !first) bv = buf[k];
-        upd(pv, gv, bv);
-        p[k] = pv;
-        if (MOM) buf[k] = bv;
-        Elem<Mdl, float>::st(q, k, pv);
-      }
-    }
-  }
+static SgdArgs sgd_args(double lr, double momentum, double dampening, double weight_decay, bool nesterov,
+                        bool maximize, bool first_step, const c10::optional<at::Tensor>& grad_scale) {
+  return {(float)lr,  (float)momentum, (float)dampening, (float)weight_decay,
+          nesterov,   maximize,        first_step,       scale_ptr(grad_scale)};
 }
 
 void fused_sgd_master(const std::vector<at::Tensor>& masters, const std::vector<at::Tensor>& grads,
@@ -671,18 +677,14 @@ void fused_sgd_master(const std::vector<at::Tensor>& masters, const std::vector<
     ptrs.push_back({masters[i].data_ptr(), const_cast<void*>(grads[i].data_ptr()), b, model_params[i].data_ptr()});
     numels.push_back(masters[i].numel());
   }
-  const float* gs = scale_ptr(grad_scale);
+  const SgdArgs args = sgd_args(lr, momentum, dampening, weight_decay, nesterov, maximize, first_step, grad_scale);
   TORCH_CHECK(mt == at::kBFloat16 || mt == at::kHalf, "master-weight SGD: model params must be bf16/fp16");
   XDDP_DISPATCH_FLOAT(gt, G, {
     auto go = [&](auto tag) {
       using Mdl = decltype(tag);
-      for_each_table<4>(ptrs, numels, [&](const SegTable<4>& t, int32_t nb) {
-        auto k = vec ? (mom ? sgd_master_kernel<G, Mdl, true, true> : sgd_master_kernel<G, Mdl, true, false>)
-                     : (mom ? sgd_master_kernel<G, Mdl, false, true> : sgd_master_kernel<G, Mdl, false, false>);
-        hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t, (float)lr, (float)momentum, (float)dampening,
-                           (float)weight_decay, nesterov, maximize, first_step, gs);
-        XDDP_HIP_CHECK(hipGetLastError());
-      });
+      launch_list<4>(vec ? (mom ? sgd_kernel<Mdl, G, true, true, true> : sgd_kernel<Mdl, G, true, false, true>)
+                         : (mom ? sgd_kernel<Mdl, G, false, true, true> : sgd_kernel<Mdl, G, false, false, true>),
+                     ptrs, numels, args, stream);
     };
     if (mt == at::kBFloat16) go(bf16_t{}); else go(f16_t{});
   });
@@ -713,171 +715,59 @@ void fused_sgd(const std::vector<at::Tensor>& params, const std::vector<at::Tens
     numels.push_back(params[i].numel());
     vec = vec && aligned16(params[i].data_ptr()) && aligned16(grads[i].data_ptr()) && (!mom || aligned16(b));
   }
-  const float* gs = scale_ptr(grad_scale);
+  const SgdArgs args = sgd_args(lr, momentum, dampening, weight_decay, nesterov, maximize, first_step, grad_scale);
   TORCH_CHECK(pt != at::kDouble && gt != at::kDouble, "fused SGD: fp64 unsupported");
   XDDP_DISPATCH_FLOAT(pt, P, XDDP_DISPATCH_FLOAT(gt, G, {
-    for_each_table<3>(ptrs, numels, [&](const SegTable<3>& t, int32_t nb) {
-      auto k = vec ? (mom ? sgd_kernel<P, G, true, true> : sgd_kernel<P, G, true, false>)
-                   : (mom ? sgd_kernel<P, G, false, true> : sgd_kernel<P, G, false, false>);
-      hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t, (float)lr, (float)momentum, (float)dampening,
-                         (float)weight_decay, nesterov, maximize, first_step, gs);
-      XDDP_HIP_CHECK(hipGetLastError());
-    });
+    launch_list<3>(vec ? (mom ? sgd_kernel<P, G, true, true, false> : sgd_kernel<P, G, true, false, false>)
+                       : (mom ? sgd_kernel<P, G, false, true, false> : sgd_kernel<P, G, false, false, false>),
+                   ptrs, numels, args, stream);
   }));
 }
 
 // ------------------------------------------------------------------------------------
-// Fused Adam / AdamW: slots {param, grad, exp_avg, exp_avg_sq, master}
+// Fused Adam / AdamW: the update, its hyperparameters and the parameter write that the kernel with
+// fp32 moments and the one with 8-bit moments share
 // ------------------------------------------------------------------------------------
-template <typename P, typename G, bool VEC, bool MASTER>
-__global__ __launch_bounds__(kThreads) void adam_kernel(SegTable<5> t, float lr, float b1, float b2, float omb1,
-    float omb2, float eps,
-                                                        float wd, float bc1, float bc2_sqrt, bool decoupled,
-                                                        bool maximize, const float* gs) {
-  const int s = find_seg(t, blockIdx.x);
-  const int64_t blk = blockIdx.x - (s ? t.blk_end[s - 1] : 0);
-  P* p = reinterpret_cast<P*>(t.ptr[0][s]);
-  const G* g = reinterpret_cast<const G*>(t.ptr[1][s]);
-  float* m = reinterpret_cast<float*>(t.ptr[2][s]);
-  float* v = reinterpret_cast<float*>(t.ptr[3][s]);
-  float* mp = reinterpret_cast<float*>(t.ptr[4][s]);
-  const int64_t n = t.numel[s];
-  const float gscale = (gs ? *gs : 1.f) * (maximize ? -1.f : 1.f);
-  const float step_size = lr / bc1;
-  const int64_t base = blk * kChunk;
-  // omb1 / omb2 are 1 - beta1 / 1 - beta2 formed in fp64 on the host: 1.f - b2 from the rounded b2 = 0.999f
-  // is 1.3e-5 off, which exp_avg_sq and the denominator would carry.
-  auto upd = [&](float& pv, float gv, float& mv, float& vv) {
-    float gg = gv * gscale;
-    if (wd != 0.f) {
-      if (decoupled) pv *= (1.f - lr * wd);
-      else gg = fmaf(wd, pv, gg);
-    }
-    mv = fmaf(b1, mv, omb1 * gg);
-    vv = fmaf(b2, vv, omb2 * gg * gg);
-    const float denom = sqrtf(vv) / bc2_sqrt + eps;
-    pv = pv - step_size * mv / denom;
-  };
-  if (VEC && base + kChunk <= n) {
-    // whole chunk: every iteration's loads first, then the updates and stores. (Interleaved, the
-    // stores of iteration it may alias the loads of it + 1 for the compiler, so each iteration's 7
-    // loads waited alone: 112 B in flight per thread instead of 448 B.)
-    float pv[kIters][8], gv[kIters][8], mv[kIters][8], vv[kIters][8];
-#pragma unroll
-    for (int it = 0; it < kIters; ++it) {
-      const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
-      if (MASTER) Vec8<float>::ld(mp + i, pv[it]); else Vec8<P>::ld(p + i, pv[it]);
-      Vec8<G>::ld(g + i, gv[it]);
-      Vec8<float>::ld(m + i, mv[it]);
-      Vec8<float>::ld(v + i, vv[it]);
-    }
-#pragma unroll
-    for (int it = 0; it < kIters; ++it) {
-      const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) upd(pv[it][j], gv[it][j], mv[it][j], vv[it][j]);
-      Vec8<P>::st(p + i, pv[it]);
-      if (MASTER) Vec8<float>::st(mp + i, pv[it]);
-      Vec8<float>::st(m + i, mv[it]);
-      Vec8<float>::st(v + i, vv[it]);
-    }
-    return;
-  }
-#pragma unroll
-  for (int it = 0; it < kIters; ++it) {
-    const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
-    if (VEC && i + 8 <= n) {
-      float pv[8], gv[8], mv[8], vv[8];
-      if (MASTER) Vec8<float>::ld(mp + i, pv); else Vec8<P>::ld(p + i, pv);
-      Vec8<G>::ld(g + i, gv);
-      Vec8<float>::ld(m + i, mv);
-      Vec8<float>::ld(v + i, vv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) upd(pv[j], gv[j], mv[j], vv[j]);
-      Vec8<P>::st(p + i, pv);
-      if (MASTER) Vec8<float>::st(mp + i, pv);
-      Vec8<float>::st(m + i, mv);
-      Vec8<float>::st(v + i, vv);
-    } else {
-      for (int64_t k = i; k < i + 8 && k < n; ++k) {
-        float pv = MASTER ? mp[k] : Elem<P, float>::ld(p, k);
-        float gv = Elem<G, float>::ld(g, k), mv = m[k], vv = v[k];
-        upd(pv, gv, mv, vv);
-        Elem<P, float>::st(p, k, pv);
-        if (MASTER) mp[k] = pv;
-        m[k] = mv;
-        v[k] = vv;
-      }
-    }
-  }
-}
+struct AdamArgs {
+  float lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2_sqrt;
+  bool decoupled, maximize;
+  const float* gs;
+};
+// ... and what keys the stochastic rounding (the 8-bit moments', the bf16 parameter write's)
+struct AdamSrArgs : AdamArgs {
+  unsigned long long seed;
+  uint32_t step;
+};
 
-void fused_adam(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
-                const std::vector<at::Tensor>& exp_avgs, const std::vector<at::Tensor>& exp_avg_sqs,
-                const std::vector<at::Tensor>& masters, double lr, double beta1, double beta2, double eps,
-                double weight_decay, int64_t step, bool decoupled, bool maximize,
-                const c10::optional<at::Tensor>& grad_scale, hipStream_t stream) {
-  const size_t N = params.size();
-  TORCH_CHECK(grads.size() == N && exp_avgs.size() == N && exp_avg_sqs.size() == N, "adam: list length mismatch");
-  const bool has_master = !masters.empty();
-  TORCH_CHECK(!has_master || masters.size() == N, "adam: masters length mismatch");
-  if (N == 0) return;
-  TORCH_CHECK(step >= 1, "adam: step must be >= 1");
-  const auto pt = params[0].scalar_type(), gt = grads[0].scalar_type();
-  TORCH_CHECK(pt != at::kDouble && gt != at::kDouble, "fused Adam: fp64 unsupported");
-  std::vector<std::array<void*, 5>> ptrs;
-  std::vector<int64_t> numels;
-  bool vec = true;
-  for (size_t i = 0; i < N; ++i) {
-    TORCH_CHECK(params[i].scalar_type() == pt && grads[i].scalar_type() == gt, "mixed dtypes in Adam list");
-    TORCH_CHECK(exp_avgs[i].scalar_type() == at::kFloat && exp_avg_sqs[i].scalar_type() == at::kFloat,
-                "Adam states must be fp32");
-    check_dense_pair(params[i], grads[i]);
-    check_dense_pair(params[i], exp_avgs[i]);
-    check_dense_pair(params[i], exp_avg_sqs[i]);
-    void* mp = nullptr;
-    if (has_master) {
-      TORCH_CHECK(masters[i].scalar_type() == at::kFloat, "master weights must be fp32");
-      check_dense_pair(params[i], masters[i]);
-      mp = masters[i].data_ptr();
-    }
-    ptrs.push_back({params[i].data_ptr(), const_cast<void*>(grads[i].data_ptr()), exp_avgs[i].data_ptr(),
-                    exp_avg_sqs[i].data_ptr(), mp});
-    numels.push_back(params[i].numel());
-    for (auto* q : ptrs.back()) vec = vec && (q == nullptr || aligned16(q));
-  }
+// The only place where 1 - beta, the bias corrections and sqrt(bc2) are formed. omb1 / omb2 are
+// 1 - beta1 / 1 - beta2 formed in fp64: 1.f - b2 from the rounded b2 = 0.999f is 1.3e-5 off, which
+// exp_avg_sq and the denominator would carry.
+static AdamArgs adam_args(double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                          bool decoupled, bool maximize, const c10::optional<at::Tensor>& grad_scale) {
   const double bc1 = 1.0 - std::pow(beta1, (double)step);
   const double bc2 = 1.0 - std::pow(beta2, (double)step);
-  const float* gs = scale_ptr(grad_scale);
-  XDDP_DISPATCH_FLOAT(pt, P, XDDP_DISPATCH_FLOAT(gt, G, {
-    for_each_table<5>(ptrs, numels, [&](const SegTable<5>& t, int32_t nb) {
-      auto k = vec ? (has_master ? adam_kernel<P, G, true, true> : adam_kernel<P, G, true, false>)
-                   : (has_master ? adam_kernel<P, G, false, true> : adam_kernel<P, G, false, false>);
-      hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t, (float)lr, (float)beta1, (float)beta2,
-                         (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)bc1, (float)std::sqrt(bc2), decoupled, maximize, gs);
-      XDDP_HIP_CHECK(hipGetLastError());
-    });
-  }));
+  return {(float)lr,  (float)beta1,        (float)beta2,          (float)(1.0 - beta1), (float)(1.0 - beta2),
+          (float)eps, (float)weight_decay, (float)bc1,            (float)std::sqrt(bc2), decoupled,
+          maximize,   scale_ptr(grad_scale)};
 }
 
-// ------------------------------------------------------------------------------------
-// Fused Adam / AdamW with 8-bit moments: slots {param, grad, m codes, m scales, s codes, s scales,
-// master, parameter ordinal, element offset of the range within its parameter}
-//
-// Both moments are OCP e4m3 codes with one fp32 scale per group of 128 consecutive elements
-// (scale = group max / 448); the second moment is stored as s = sqrt(v). A block's 8192-element chunk
-// is 64 whole groups, and a group is 16 adjacent lanes x 8 elements, so the two group maxima are
-// reduced over a DPP row (no LDS, no barrier). The update itself is adam_kernel's `upd`, on the
-// dequantised fp32 moments; the parameter uses the fresh fp32 moments, which are re-quantised
-// afterwards with stochastic rounding (v_cvt_sr_fp8_f32). The random bits are a stateless hash of
-// (seed, parameter ordinal, step, element index within the parameter, moment), so they do not
-// depend on the launch, the segment table, the load path or on slicing. Loads and stores differ
-// between the vector path, the tail and the unaligned path; everything in between is one function.
-// ------------------------------------------------------------------------------------
-constexpr int kQGroup = 128;
-constexpr float kE4M3Max = 448.f;
-static_assert(kChunk % kQGroup == 0 && kQGroup == 16 * 8, "a group is one DPP row of 8-element lanes");
-static_assert(sizeof(SegTable<9>) + 128 <= 4096, "the by-value segment table must fit the kernarg segment");
+struct AdamUpdate {
+  const AdamArgs& a;
+  const float gscale, step_size;
+  __device__ __forceinline__ explicit AdamUpdate(const AdamArgs& a_)
+      : a(a_), gscale((a_.gs ? *a_.gs : 1.f) * (a_.maximize ? -1.f : 1.f)), step_size(a_.lr / a_.bc1) {}
+  __device__ __forceinline__ void operator()(float& pv, float gv, float& mv, float& vv) const {
+    float gg = gv * gscale;
+    if (a.wd != 0.f) {
+      if (a.decoupled) pv *= (1.f - a.lr * a.wd);
+      else gg = fmaf(a.wd, pv, gg);
+    }
+    mv = fmaf(a.b1, mv, a.omb1 * gg);
+    vv = fmaf(a.b2, vv, a.omb2 * gg * gg);
+    const float denom = sqrtf(vv) / a.bc2_sqrt + a.eps;
+    pv = pv - step_size * mv / denom;
+  }
+};
 
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {  // 2-round multiply-xorshift finalizer
   x ^= x >> 16;
@@ -887,9 +777,13 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {  // 2-round multiply-xor
   return x ^ (x >> 16);
 }
 
-// Stochastically rounded bf16 parameter write. `key` is the hash key of (seed, ordinal, step) whose
-// low / high half are the moments' km / ks; the parameter write's key kp is the splitmix64 output
-// after it, a third stream.
+// The hash key of (seed, parameter ordinal, step): its low / high half are the 8-bit moments' km / ks
+__device__ __forceinline__ unsigned long long sr_key(unsigned long long seed, unsigned long long ordinal,
+                                                     uint32_t step) {
+  return mix64(seed ^ mix64((ordinal << 32) | step));
+}
+// Stochastically rounded bf16 parameter write: its key kp is the splitmix64 output after `key`, a
+// third stream.
 __device__ __forceinline__ uint32_t sr_param_key(unsigned long long key) {
   return (uint32_t)mix64(key + 0x9e3779b97f4a7c15ull);
 }
@@ -913,6 +807,216 @@ __device__ __forceinline__ void st8_sr_bf16(bf16_t* p, const float (&v)[8], int6
     a[j] = sr_bf16(v[2 * j], e0 + 2 * j, kp) | (sr_bf16(v[2 * j + 1], e0 + 2 * j + 1, kp) << 16);
   *reinterpret_cast<dev::u32x4*>(p) = a;
 }
+
+// How an Adam kernel writes the updated parameter: rounded to nearest in P, or (SR: bf16 parameters
+// without a master) with sr_bf16. The random bits hang on the element's index within its parameter
+// (`eoff` is that of the range's first element), so any slicing gives the bits of the
+// whole-parameter update.
+template <typename P, bool SR>
+struct ParamWriter {
+  static_assert(!SR || std::is_same<P, bf16_t>::value, "stochastic rounding: bf16 parameters");
+  P* p;
+  int64_t eoff;
+  uint32_t kp;
+  // the 8 elements from range index i on (16-byte store), and element k alone
+  __device__ __forceinline__ void st8(int64_t i, const float (&pv)[8]) const {
+    if constexpr (SR) st8_sr_bf16(p + i, pv, eoff + i, kp);
+    else Vec8<P>::st(p + i, pv);
+  }
+  __device__ __forceinline__ void st(int64_t k, float pv) const {
+    if constexpr (SR) p[k].x = (uint16_t)sr_bf16(pv, eoff + k, kp);
+    else Elem<P, float>::st(p, k, pv);
+  }
+};
+
+// Validates the lists of one Adam launch (lengths are the caller's): every tensor on the device, one
+// dtype per list (fp32 for `states` and `masters`), each dense in its parameter's memory order, and
+// ordinals / offsets (where the launch has them) in range.
+static void check_adam_lists(const char* who, const std::vector<at::Tensor>& params,
+                             const std::vector<at::Tensor>& grads,
+                             std::initializer_list<const std::vector<at::Tensor>*> states,
+                             const std::vector<at::Tensor>& masters, const std::vector<int64_t>* ordinals,
+                             const std::vector<int64_t>* offsets) {
+  const auto pt = params[0].scalar_type(), gt = grads[0].scalar_type();
+  for (size_t i = 0; i < params.size(); ++i) {
+    const at::Tensor& p = params[i];
+    TORCH_CHECK(p.is_cuda() && grads[i].is_cuda() && p.scalar_type() == pt && grads[i].scalar_type() == gt, who,
+                ": device tensors of one dtype per list expected");
+    check_dense_pair(p, grads[i]);
+    for (const auto* list : states) {
+      const at::Tensor& x = (*list)[i];
+      TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat, who, ": Adam states must be fp32 device tensors");
+      check_dense_pair(p, x);
+    }
+    if (!masters.empty()) {
+      TORCH_CHECK(masters[i].is_cuda() && masters[i].scalar_type() == at::kFloat, "master weights must be fp32");
+      check_dense_pair(p, masters[i]);
+    }
+    TORCH_CHECK(!ordinals || ((*ordinals)[i] >= 0 && (*ordinals)[i] <= (int64_t)UINT32_MAX && (*offsets)[i] >= 0),
+                who, ": bad parameter ordinal or offset");
+  }
+}
+
+// ------------------------------------------------------------------------------------
+// Fused Adam / AdamW with fp32 moments: slots {param, grad, exp_avg, exp_avg_sq, master}, or, for
+// stochastically rounded bf16 parameters (SR: no master), {param, grad, exp_avg, exp_avg_sq,
+// parameter ordinal, element offset of the range within its parameter}
+// ------------------------------------------------------------------------------------
+template <typename P, typename G, bool VEC, bool MASTER, bool SR = false>
+__global__ __launch_bounds__(kThreads) void adam_kernel(SegTable<SR ? 6 : 5> t,
+                                                        std::conditional_t<SR, AdamSrArgs, AdamArgs> a) {
+  static_assert(!SR || !MASTER, "stochastic rounding: no master");
+  const Chunk c = block_chunk(t);
+  P* p = reinterpret_cast<P*>(t.ptr[0][c.s]);
+  const G* g = reinterpret_cast<const G*>(t.ptr[1][c.s]);
+  float* m = reinterpret_cast<float*>(t.ptr[2][c.s]);
+  float* v = reinterpret_cast<float*>(t.ptr[3][c.s]);
+  float* mp = nullptr;
+  ParamWriter<P, SR> w{p, 0, 0u};
+  if constexpr (SR) {
+    w.eoff = (int64_t)reinterpret_cast<uintptr_t>(t.ptr[5][c.s]);
+    w.kp = sr_param_key(sr_key(a.seed, reinterpret_cast<uintptr_t>(t.ptr[4][c.s]), a.step));
+  } else {
+    mp = reinterpret_cast<float*>(t.ptr[4][c.s]);
+  }
+  const int64_t n = c.n;
+  const AdamUpdate upd(a);
+  if (VEC && c.base + kChunk <= n) {
+    // whole chunk: every iteration's loads first, then the updates and stores. (Interleaved, the
+    // stores of iteration it may alias the loads of it + 1 for the compiler, so each iteration's 7
+    // loads waited alone: 112 B in flight per thread instead of 448 B.)
+    float pv[kIters][8], gv[kIters][8], mv[kIters][8], vv[kIters][8];
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int64_t i = c.base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+      if (MASTER) Vec8<float>::ld(mp + i, pv[it]); else Vec8<P>::ld(p + i, pv[it]);
+      Vec8<G>::ld(g + i, gv[it]);
+      Vec8<float>::ld(m + i, mv[it]);
+      Vec8<float>::ld(v + i, vv[it]);
+    }
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int64_t i = c.base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) upd(pv[it][j], gv[it][j], mv[it][j], vv[it][j]);
+      w.st8(i, pv[it]);
+      if (MASTER) Vec8<float>::st(mp + i, pv[it]);
+      Vec8<float>::st(m + i, mv[it]);
+      Vec8<float>::st(v + i, vv[it]);
+    }
+    return;
+  }
+#pragma unroll
+  for (int it = 0; it < kIters; ++it) {
+    const int64_t i = c.base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+    if (VEC && i + 8 <= n) {
+      float pv[8], gv[8], mv[8], vv[8];
+      if (MASTER) Vec8<float>::ld(mp + i, pv); else Vec8<P>::ld(p + i, pv);
+      Vec8<G>::ld(g + i, gv);
+      Vec8<float>::ld(m + i, mv);
+      Vec8<float>::ld(v + i, vv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) upd(pv[j], gv[j], mv[j], vv[j]);
+      w.st8(i, pv);
+      if (MASTER) Vec8<float>::st(mp + i, pv);
+      Vec8<float>::st(m + i, mv);
+      Vec8<float>::st(v + i, vv);
+    } else {
+      for (int64_t k = i; k < i + 8 && k < n; ++k) {
+        float pv = MASTER ? mp[k] : Elem<P, float>::ld(p, k);
+        float gv = Elem<G, float>::ld(g, k), mv = m[k], vv = v[k];
+        upd(pv, gv, mv, vv);
+        w.st(k, pv);
+        if (MASTER) mp[k] = pv;
+        m[k] = mv;
+        v[k] = vv;
+      }
+    }
+  }
+}
+
+void fused_adam(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                const std::vector<at::Tensor>& exp_avgs, const std::vector<at::Tensor>& exp_avg_sqs,
+                const std::vector<at::Tensor>& masters, double lr, double beta1, double beta2, double eps,
+                double weight_decay, int64_t step, bool decoupled, bool maximize,
+                const c10::optional<at::Tensor>& grad_scale, hipStream_t stream) {
+  const size_t N = params.size();
+  TORCH_CHECK(grads.size() == N && exp_avgs.size() == N && exp_avg_sqs.size() == N, "adam: list length mismatch");
+  const bool has_master = !masters.empty();
+  TORCH_CHECK(!has_master || masters.size() == N, "adam: masters length mismatch");
+  if (N == 0) return;
+  TORCH_CHECK(step >= 1, "adam: step must be >= 1");
+  const auto pt = params[0].scalar_type(), gt = grads[0].scalar_type();
+  TORCH_CHECK(pt != at::kDouble && gt != at::kDouble, "fused Adam: fp64 unsupported");
+  check_adam_lists("adam", params, grads, {&exp_avgs, &exp_avg_sqs}, masters, nullptr, nullptr);
+  std::vector<std::array<void*, 5>> ptrs;
+  std::vector<int64_t> numels;
+  bool vec = true;
+  for (size_t i = 0; i < N; ++i) {
+    ptrs.push_back({params[i].data_ptr(), const_cast<void*>(grads[i].data_ptr()), exp_avgs[i].data_ptr(),
+                    exp_avg_sqs[i].data_ptr(), has_master ? masters[i].data_ptr() : nullptr});
+    numels.push_back(params[i].numel());
+    for (auto* q : ptrs.back()) vec = vec && aligned16(q);
+  }
+  const AdamArgs args = adam_args(lr, beta1, beta2, eps, weight_decay, step, decoupled, maximize, grad_scale);
+  XDDP_DISPATCH_FLOAT(pt, P, XDDP_DISPATCH_FLOAT(gt, G, {
+    launch_list<5>(vec ? (has_master ? adam_kernel<P, G, true, true> : adam_kernel<P, G, true, false>)
+                       : (has_master ? adam_kernel<P, G, false, true> : adam_kernel<P, G, false, false>),
+                   ptrs, numels, args, stream);
+  }));
+}
+
+// Fused Adam / AdamW with fp32 moments and stochastically rounded bf16 parameters (no fp32 master)
+void fused_adam_sr(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                   const std::vector<at::Tensor>& exp_avgs, const std::vector<at::Tensor>& exp_avg_sqs,
+                   const std::vector<int64_t>& ordinals, const std::vector<int64_t>& offsets, double lr, double beta1,
+                   double beta2, double eps, double weight_decay, int64_t step, int64_t seed, bool decoupled,
+                   bool maximize, const c10::optional<at::Tensor>& grad_scale, hipStream_t stream) {
+  const char* who = "adam (stochastic rounding)";
+  const size_t N = params.size();
+  TORCH_CHECK(grads.size() == N && exp_avgs.size() == N && exp_avg_sqs.size() == N && ordinals.size() == N &&
+                  offsets.size() == N,
+              who, ": list length mismatch");
+  if (N == 0) return;
+  TORCH_CHECK(step >= 1 && step <= (int64_t)UINT32_MAX && seed >= 0, who, ": step must be in [1, 2^32), seed >= 0");
+  TORCH_CHECK(params[0].scalar_type() == at::kBFloat16, who, ": bf16 parameters expected");
+  check_adam_lists(who, params, grads, {&exp_avgs, &exp_avg_sqs}, {}, &ordinals, &offsets);
+  std::vector<std::array<void*, 6>> ptrs;
+  std::vector<int64_t> numels;
+  bool vec = true;
+  for (size_t i = 0; i < N; ++i) {
+    ptrs.push_back({params[i].data_ptr(), const_cast<void*>(grads[i].data_ptr()), exp_avgs[i].data_ptr(),
+                    exp_avg_sqs[i].data_ptr(), reinterpret_cast<void*>((uintptr_t)ordinals[i]),
+                    reinterpret_cast<void*>((uintptr_t)offsets[i])});
+    numels.push_back(params[i].numel());
+    for (int q = 0; q < 4; ++q) vec = vec && aligned16(ptrs.back()[q]);
+  }
+  const AdamSrArgs args = {adam_args(lr, beta1, beta2, eps, weight_decay, step, decoupled, maximize, grad_scale),
+                           (unsigned long long)seed, (uint32_t)step};
+  XDDP_DISPATCH_FLOAT_NO_F64(grads[0].scalar_type(), G, "fused Adam (stochastic rounding): unsupported gradient dtype ", {
+    launch_list<6>(vec ? adam_kernel<bf16_t, G, true, false, true> : adam_kernel<bf16_t, G, false, false, true>,
+                   ptrs, numels, args, stream);
+  });
+}
+
+// ------------------------------------------------------------------------------------
+// Fused Adam / AdamW with 8-bit moments: slots {param, grad, m codes, m scales, s codes, s scales,
+// master, parameter ordinal, element offset of the range within its parameter}
+//
+// Both moments are OCP e4m3 codes with one fp32 scale per group of 128 consecutive elements
+// (scale = group max / 448); the second moment is stored as s = sqrt(v). A block's 8192-element chunk
+// is 64 whole groups, and a group is 16 adjacent lanes x 8 elements, so the two group maxima are
+// reduced over a DPP row (no LDS, no barrier). The update itself is AdamUpdate, on the dequantised
+// fp32 moments; the parameter uses the fresh fp32 moments, which are re-quantised afterwards with
+// stochastic rounding (v_cvt_sr_fp8_f32). The random bits are a stateless hash of (seed, parameter
+// ordinal, step, element index within the parameter, moment), so they do not depend on the launch,
+// the segment table, the load path or on slicing. Loads and stores differ between the vector path,
+// the tail and the unaligned path; everything in between is one function.
+// ------------------------------------------------------------------------------------
+constexpr int kQGroup = 128;
+constexpr float kE4M3Max = 448.f;
+static_assert(kChunk % kQGroup == 0 && kQGroup == 16 * 8, "a group is one DPP row of 8-element lanes");
+static_assert(sizeof(SegTable<9>) + 128 <= 4096, "the by-value segment table must fit the kernarg segment");
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_max(float v) {
@@ -984,50 +1088,29 @@ __device__ __forceinline__ void adam8_quantize(const float (&m)[8], const float 
 // SR: bf16 parameters without a master, written with sr_bf16 (keyed like the moments, third stream).
 template <typename P, typename G, bool VEC, bool MASTER, bool SR = false>
 __global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr, float b1, float b2, float omb1,
-    float omb2, float eps,
-                                                         float wd, float bc1, float bc2_sqrt, bool decoupled,
-                                                         bool maximize, const float* gs, unsigned long long seed,
-                                                         uint32_t step) {
-  static_assert(!SR || (std::is_same<P, bf16_t>::value && !MASTER), "stochastic rounding: bf16 parameters, no master");
-  const int s = find_seg(t, blockIdx.x);
-  const int64_t blk = blockIdx.x - (s ? t.blk_end[s - 1] : 0);
-  P* p = reinterpret_cast<P*>(t.ptr[0][s]);
-  const G* g = reinterpret_cast<const G*>(t.ptr[1][s]);
-  uint8_t* mqp = reinterpret_cast<uint8_t*>(t.ptr[2][s]);
-  float* msp = reinterpret_cast<float*>(t.ptr[3][s]);
-  uint8_t* sqp = reinterpret_cast<uint8_t*>(t.ptr[4][s]);
-  float* ssp = reinterpret_cast<float*>(t.ptr[5][s]);
-  float* mp = reinterpret_cast<float*>(t.ptr[6][s]);
-  const unsigned long long ordinal = reinterpret_cast<uintptr_t>(t.ptr[7][s]);
-  const int64_t eoff = (int64_t)reinterpret_cast<uintptr_t>(t.ptr[8][s]);
-  const int64_t n = t.numel[s];
-  const unsigned long long key = mix64(seed ^ mix64((ordinal << 32) | step));
+                                                         float omb2, float eps, float wd, float bc1, float bc2_sqrt,
+                                                         bool decoupled, bool maximize, const float* gs,
+                                                         unsigned long long seed, uint32_t step) {
+  static_assert(!SR || !MASTER, "stochastic rounding: no master");
+  // (the hyperparameters one by one: taken as the struct, this kernel's vector instantiations came out with other
+  // code for the flags and measured 0.3 % slower, profiles/r11_multi_tensor_refactor.txt)
+  const AdamSrArgs a = {{lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2_sqrt, decoupled, maximize, gs}, seed, step};
+  const Chunk c = block_chunk(t);
+  P* p = reinterpret_cast<P*>(t.ptr[0][c.s]);
+  const G* g = reinterpret_cast<const G*>(t.ptr[1][c.s]);
+  uint8_t* mqp = reinterpret_cast<uint8_t*>(t.ptr[2][c.s]);
+  float* msp = reinterpret_cast<float*>(t.ptr[3][c.s]);
+  uint8_t* sqp = reinterpret_cast<uint8_t*>(t.ptr[4][c.s]);
+  float* ssp = reinterpret_cast<float*>(t.ptr[5][c.s]);
+  float* mp = reinterpret_cast<float*>(t.ptr[6][c.s]);
+  const int64_t eoff = (int64_t)reinterpret_cast<uintptr_t>(t.ptr[8][c.s]);
+  const int64_t n = c.n;
+  const unsigned long long key = sr_key(a.seed, reinterpret_cast<uintptr_t>(t.ptr[7][c.s]), a.step);
   const uint32_t km = (uint32_t)key, ks = (uint32_t)(key >> 32);
-  const uint32_t kp = SR ? sr_param_key(key) : 0u;
-  const float gscale = (gs ? *gs : 1.f) * (maximize ? -1.f : 1.f);
-  const float step_size = lr / bc1;
-  const int64_t base = blk * kChunk;
+  const ParamWriter<P, SR> w{p, eoff, SR ? sr_param_key(key) : 0u};
+  const AdamUpdate upd(a);
+  const int64_t base = c.base;
   const bool lead = (threadIdx.x & 15) == 0;  // the lane that writes its group's two scales
-  // the parameter's 8 elements from range index i on (16-byte store), and element k alone
-  auto st8_param = [&](int64_t i, const float (&pv)[8]) {
-    if constexpr (SR) st8_sr_bf16(p + i, pv, eoff + i, kp);
-    else Vec8<P>::st(p + i, pv);
-  };
-  auto st_param = [&](int64_t k, float pv) {
-    if constexpr (SR) p[k].x = (uint16_t)sr_bf16(pv, eoff + k, kp);
-    else Elem<P, float>::st(p, k, pv);
-  };
-  auto upd = [&](float& pv, float gv, float& mv, float& vv) {
-    float gg = gv * gscale;
-    if (wd != 0.f) {
-      if (decoupled) pv *= (1.f - lr * wd);
-      else gg = fmaf(wd, pv, gg);
-    }
-    mv = fmaf(b1, mv, omb1 * gg);
-    vv = fmaf(b2, vv, omb2 * gg * gg);
-    const float denom = sqrtf(vv) / bc2_sqrt + eps;
-    pv = pv - step_size * mv / denom;
-  };
   // dequantise, update, re-quantise one lane's 8 elements, the first `nv` of which exist
   auto update8 = [&](int64_t i, int nv, float (&pv)[8], const float (&gv)[8], uint32_t (&mq)[2], uint32_t (&sq)[2],
                      float& msc, float& ssc) {
@@ -1055,9 +1138,9 @@ __global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr
       const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
       if (MASTER) Vec8<float>::ld(mp + i, pv[it]); else Vec8<P>::ld(p + i, pv[it]);
       Vec8<G>::ld(g + i, gv[it]);
-      const uint2 a = *reinterpret_cast<const uint2*>(mqp + i), b = *reinterpret_cast<const uint2*>(sqp + i);
-      mq[it][0] = a.x; mq[it][1] = a.y;
-      sq[it][0] = b.x; sq[it][1] = b.y;
+      const uint2 cm = *reinterpret_cast<const uint2*>(mqp + i), cs = *reinterpret_cast<const uint2*>(sqp + i);
+      mq[it][0] = cm.x; mq[it][1] = cm.y;
+      sq[it][0] = cs.x; sq[it][1] = cs.y;
       msc[it] = msp[i / kQGroup];
       ssc[it] = ssp[i / kQGroup];
     }
@@ -1065,7 +1148,7 @@ __global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr
     for (int it = 0; it < kIters; ++it) {
       const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
       update8(i, 8, pv[it], gv[it], mq[it], sq[it], msc[it], ssc[it]);
-      st8_param(i, pv[it]);
+      w.st8(i, pv[it]);
       if (MASTER) Vec8<float>::st(mp + i, pv[it]);
       *reinterpret_cast<uint2*>(mqp + i) = make_uint2(mq[it][0], mq[it][1]);
       *reinterpret_cast<uint2*>(sqp + i) = make_uint2(sq[it][0], sq[it][1]);
@@ -1089,9 +1172,9 @@ __global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr
     if (VEC && nv == 8) {
       if (MASTER) Vec8<float>::ld(mp + i, pv); else Vec8<P>::ld(p + i, pv);
       Vec8<G>::ld(g + i, gv);
-      const uint2 a = *reinterpret_cast<const uint2*>(mqp + i), b = *reinterpret_cast<const uint2*>(sqp + i);
-      mq[0] = a.x; mq[1] = a.y;
-      sq[0] = b.x; sq[1] = b.y;
+      const uint2 cm = *reinterpret_cast<const uint2*>(mqp + i), cs = *reinterpret_cast<const uint2*>(sqp + i);
+      mq[0] = cm.x; mq[1] = cm.y;
+      sq[0] = cs.x; sq[1] = cs.y;
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -1110,7 +1193,7 @@ __global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr
     }
     update8(i, nv, pv, gv, mq, sq, msc, ssc);
     if (VEC && nv == 8) {
-      st8_param(i, pv);
+      w.st8(i, pv);
       if (MASTER) Vec8<float>::st(mp + i, pv);
       *reinterpret_cast<uint2*>(mqp + i) = make_uint2(mq[0], mq[1]);
       *reinterpret_cast<uint2*>(sqp + i) = make_uint2(sq[0], sq[1]);
@@ -1118,7 +1201,7 @@ __global__ __launch_bounds__(kThreads) void adam8_kernel(SegTable<9> t, float lr
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         if (j < nv) {
-          st_param(i + j, pv[j]);
+          w.st(i + j, pv[j]);
           if (MASTER) mp[i + j] = pv[j];
           mqp[i + j] = (uint8_t)(mq[j >> 2] >> (8 * (j & 3)));
           sqp[i + j] = (uint8_t)(sq[j >> 2] >> (8 * (j & 3)));
@@ -1151,28 +1234,19 @@ void fused_adam8(const std::vector<at::Tensor>& params, const std::vector<at::Te
   TORCH_CHECK(pt != at::kDouble && gt != at::kDouble, "fused Adam: fp64 unsupported");
   TORCH_CHECK(!stochastic_params || (pt == at::kBFloat16 && !has_master),
               "adam8: stochastic parameter rounding is for bf16 parameters without master weights");
+  check_adam_lists("adam8", params, grads, {}, masters, &ordinals, &group_offsets);
   std::vector<std::array<void*, 9>> ptrs;
   std::vector<int64_t> numels;
   bool vec = true;
   for (size_t i = 0; i < N; ++i) {
     const int64_t n = params[i].numel(), ng = (n + kQGroup - 1) / kQGroup;
-    TORCH_CHECK(params[i].is_cuda() && params[i].scalar_type() == pt && grads[i].scalar_type() == gt,
-                "adam8: device tensors of one dtype per list expected");
-    check_dense_pair(params[i], grads[i]);
     for (const at::Tensor* q : {&m_q[i], &s_q[i]})
       TORCH_CHECK(q->is_cuda() && q->scalar_type() == at::kByte && q->is_contiguous() && q->numel() == n,
                   "adam8: moment codes must be contiguous uint8 device tensors of the parameter's numel");
     for (const at::Tensor* q : {&m_scale[i], &s_scale[i]})
       TORCH_CHECK(q->is_cuda() && q->scalar_type() == at::kFloat && q->is_contiguous() && q->numel() == ng,
                   "adam8: moment scales must be contiguous fp32 device tensors, one entry per 128 elements");
-    TORCH_CHECK(ordinals[i] >= 0 && ordinals[i] <= (int64_t)UINT32_MAX && group_offsets[i] >= 0,
-                "adam8: bad parameter ordinal or group offset");
-    void* mp = nullptr;
-    if (has_master) {
-      TORCH_CHECK(masters[i].is_cuda() && masters[i].scalar_type() == at::kFloat, "master weights must be fp32");
-      check_dense_pair(params[i], masters[i]);
-      mp = masters[i].data_ptr();
-    }
+    void* mp = has_master ? masters[i].data_ptr() : nullptr;
     ptrs.push_back({params[i].data_ptr(), const_cast<void*>(grads[i].data_ptr()), m_q[i].data_ptr(),
                     m_scale[i].data_ptr(), s_q[i].data_ptr(), s_scale[i].data_ptr(), mp,
                     reinterpret_cast<void*>((uintptr_t)ordinals[i]),
@@ -1182,49 +1256,36 @@ void fused_adam8(const std::vector<at::Tensor>& params, const std::vector<at::Te
           (reinterpret_cast<uintptr_t>(m_q[i].data_ptr()) & 7u) == 0 &&
           (reinterpret_cast<uintptr_t>(s_q[i].data_ptr()) & 7u) == 0;
   }
-  const double bc1 = 1.0 - std::pow(beta1, (double)step);
-  const double bc2 = 1.0 - std::pow(beta2, (double)step);
-  const float* gs = scale_ptr(grad_scale);
-  // (no fp64 instantiations: the dtype check above has already refused them)
-#define XDDP_DISPATCH_ADAM8(st, NAME, ...)                           \
-  switch (st) {                                                      \
-    case at::kFloat: { using NAME = float; __VA_ARGS__; break; }     \
-    case at::kBFloat16: { using NAME = bf16_t; __VA_ARGS__; break; } \
-    case at::kHalf: { using NAME = f16_t; __VA_ARGS__; break; }      \
-    default: TORCH_CHECK(false, "fused Adam (8-bit states): unsupported dtype ", st); \
-  }
+  const AdamArgs a = adam_args(lr, beta1, beta2, eps, weight_decay, step, decoupled, maximize, grad_scale);
   auto launch = [&](auto k) {
     for_each_table<9>(ptrs, numels, [&](const SegTable<9>& t, int32_t nb) {
-      hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t, (float)lr, (float)beta1, (float)beta2,
-                         (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)bc1, (float)std::sqrt(bc2), decoupled, maximize, gs,
-                         (unsigned long long)seed, (uint32_t)step);
+      hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t, a.lr, a.b1, a.b2, a.omb1, a.omb2, a.eps, a.wd,
+                         a.bc1, a.bc2_sqrt, a.decoupled, a.maximize, a.gs, (unsigned long long)seed, (uint32_t)step);
       XDDP_HIP_CHECK(hipGetLastError());
     });
   };
+  // (no fp64 instantiations: the dtype check above has already refused them)
+  const char* bad = "fused Adam (8-bit states): unsupported dtype ";
   if (stochastic_params) {
-    XDDP_DISPATCH_ADAM8(gt, G, launch(vec ? adam8_kernel<bf16_t, G, true, false, true>
-                                          : adam8_kernel<bf16_t, G, false, false, true>));
+    XDDP_DISPATCH_FLOAT_NO_F64(gt, G, bad, {
+      launch(vec ? adam8_kernel<bf16_t, G, true, false, true> : adam8_kernel<bf16_t, G, false, false, true>);
+    });
   } else {
-    XDDP_DISPATCH_ADAM8(pt, P, XDDP_DISPATCH_ADAM8(gt, G, {
+    XDDP_DISPATCH_FLOAT_NO_F64(pt, P, bad, XDDP_DISPATCH_FLOAT_NO_F64(gt, G, bad, {
       launch(vec ? (has_master ? adam8_kernel<P, G, true, true> : adam8_kernel<P, G, true, false>)
                  : (has_master ? adam8_kernel<P, G, false, true> : adam8_kernel<P, G, false, false>));
     }));
   }
-#undef XDDP_DISPATCH_ADAM8
 }
 
 // ------------------------------------------------------------------------------------
-// Stochastically rounded bf16 parameters (no fp32 master): the rounding alone, and fused Adam /
-// AdamW with fp32 moments whose parameter write is sr_bf16. Slots of the latter: {param, grad,
-// exp_avg, exp_avg_sq, parameter ordinal, element offset of the range within its parameter}. The
-// random bits hang on the element's index within its parameter, so any slicing gives the bits of
-// the whole-parameter update. (adam8_kernel<.., SR = true> is the same write with 8-bit moments.)
+// The stochastic rounding alone: fp32 -> bf16 with sr_bf16, keyed like the optimizers' parameter write
 // ------------------------------------------------------------------------------------
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void sr_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ out,
                                                            int64_t n, unsigned long long seed,
                                                            unsigned long long ordinal, uint32_t step, int64_t eoff) {
-  const uint32_t kp = sr_param_key(mix64(seed ^ mix64((ordinal << 32) | step)));
+  const uint32_t kp = sr_param_key(sr_key(seed, ordinal, step));
   const int64_t base = (int64_t)blockIdx.x * kChunk;
 #pragma unroll
   for (int it = 0; it < kIters; ++it) {
@@ -1259,135 +1320,6 @@ void stochastic_round_bf16(const at::Tensor& x, const at::Tensor& out, int64_t s
   XDDP_HIP_CHECK(hipGetLastError());
 }
 
-template <typename G, bool VEC>
-__global__ __launch_bounds__(kThreads) void adam_sr_kernel(SegTable<6> t, float lr, float b1, float b2, float omb1,
-    float omb2, float eps,
-                                                           float wd, float bc1, float bc2_sqrt, bool decoupled,
-                                                           bool maximize, const float* gs, unsigned long long seed,
-                                                           uint32_t step) {
-  const int s = find_seg(t, blockIdx.x);
-  const int64_t blk = blockIdx.x - (s ? t.blk_end[s - 1] : 0);
-  bf16_t* p = reinterpret_cast<bf16_t*>(t.ptr[0][s]);
-  const G* g = reinterpret_cast<const G*>(t.ptr[1][s]);
-  float* m = reinterpret_cast<float*>(t.ptr[2][s]);
-  float* v = reinterpret_cast<float*>(t.ptr[3][s]);
-  const unsigned long long ordinal = reinterpret_cast<uintptr_t>(t.ptr[4][s]);
-  const int64_t eoff = (int64_t)reinterpret_cast<uintptr_t>(t.ptr[5][s]);
-  const int64_t n = t.numel[s];
-  const uint32_t kp = sr_param_key(mix64(seed ^ mix64((ordinal << 32) | step)));
-  const float gscale = (gs ? *gs : 1.f) * (maximize ? -1.f : 1.f);
-  const float step_size = lr / bc1;
-  const int64_t base = blk * kChunk;
-  auto upd = [&](float& pv, float gv, float& mv, float& vv) {  // adam_kernel's, to the letter
-    float gg = gv * gscale;
-    if (wd != 0.f) {
-      if (decoupled) pv *= (1.f - lr * wd);
-      else gg = fmaf(wd, pv, gg);
-    }
-    mv = fmaf(b1, mv, omb1 * gg);
-    vv = fmaf(b2, vv, omb2 * gg * gg);
-    const float denom = sqrtf(vv) / bc2_sqrt + eps;
-    pv = pv - step_size * mv / denom;
-  };
-  if (VEC && base + kChunk <= n) {
-    // whole chunk: every iteration's loads first, then the updates and stores (as adam_kernel)
-    float pv[kIters][8], gv[kIters][8], mv[kIters][8], vv[kIters][8];
-#pragma unroll
-    for (int it = 0; it < kIters; ++it) {
-      const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
-      Vec8<bf16_t>::ld(p + i, pv[it]);
-      Vec8<G>::ld(g + i, gv[it]);
-      Vec8<float>::ld(m + i, mv[it]);
-      Vec8<float>::ld(v + i, vv[it]);
-    }
-#pragma unroll
-    for (int it = 0; it < kIters; ++it) {
-      const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) upd(pv[it][j], gv[it][j], mv[it][j], vv[it][j]);
-      st8_sr_bf16(p + i, pv[it], eoff + i, kp);
-      Vec8<float>::st(m + i, mv[it]);
-      Vec8<float>::st(v + i, vv[it]);
-    }
-    return;
-  }
-#pragma unroll
-  for (int it = 0; it < kIters; ++it) {
-    const int64_t i = base + ((int64_t)it * kThreads + threadIdx.x) * 8;
-    if (VEC && i + 8 <= n) {
-      float pv[8], gv[8], mv[8], vv[8];
-      Vec8<bf16_t>::ld(p + i, pv);
-      Vec8<G>::ld(g + i, gv);
-      Vec8<float>::ld(m + i, mv);
-      Vec8<float>::ld(v + i, vv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) upd(pv[j], gv[j], mv[j], vv[j]);
-      st8_sr_bf16(p + i, pv, eoff + i, kp);
-      Vec8<float>::st(m + i, mv);
-      Vec8<float>::st(v + i, vv);
-    } else {
-      for (int64_t k = i; k < i + 8 && k < n; ++k) {
-        float pv = Elem<bf16_t, float>::ld(p, k), gv = Elem<G, float>::ld(g, k), mv = m[k], vv = v[k];
-        upd(pv, gv, mv, vv);
-        p[k].x = (uint16_t)sr_bf16(pv, eoff + k, kp);
-        m[k] = mv;
-        v[k] = vv;
-      }
-    }
-  }
-}
-
-void fused_adam_sr(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
-                   const std::vector<at::Tensor>& exp_avgs, const std::vector<at::Tensor>& exp_avg_sqs,
-                   const std::vector<int64_t>& ordinals, const std::vector<int64_t>& offsets, double lr, double beta1,
-                   double beta2, double eps, double weight_decay, int64_t step, int64_t seed, bool decoupled,
-                   bool maximize, const c10::optional<at::Tensor>& grad_scale, hipStream_t stream) {
-  const size_t N = params.size();
-  TORCH_CHECK(grads.size() == N && exp_avgs.size() == N && exp_avg_sqs.size() == N && ordinals.size() == N &&
-                  offsets.size() == N,
-              "adam (stochastic rounding): list length mismatch");
-  if (N == 0) return;
-  TORCH_CHECK(step >= 1 && step <= (int64_t)UINT32_MAX && seed >= 0,
-              "adam (stochastic rounding): step must be in [1, 2^32), seed >= 0");
-  const auto gt = grads[0].scalar_type();
-  std::vector<std::array<void*, 6>> ptrs;
-  std::vector<int64_t> numels;
-  bool vec = true;
-  for (size_t i = 0; i < N; ++i) {
-    TORCH_CHECK(params[i].is_cuda() && params[i].scalar_type() == at::kBFloat16 && grads[i].scalar_type() == gt,
-                "adam (stochastic rounding): bf16 device parameters and gradients of one dtype expected");
-    TORCH_CHECK(grads[i].is_cuda() && exp_avgs[i].is_cuda() && exp_avg_sqs[i].is_cuda() &&
-                    exp_avgs[i].scalar_type() == at::kFloat && exp_avg_sqs[i].scalar_type() == at::kFloat,
-                "adam (stochastic rounding): gradients and fp32 states on the device expected");
-    check_dense_pair(params[i], grads[i]);
-    check_dense_pair(params[i], exp_avgs[i]);
-    check_dense_pair(params[i], exp_avg_sqs[i]);
-    TORCH_CHECK(ordinals[i] >= 0 && ordinals[i] <= (int64_t)UINT32_MAX && offsets[i] >= 0,
-                "adam (stochastic rounding): bad parameter ordinal or element offset");
-    ptrs.push_back({params[i].data_ptr(), const_cast<void*>(grads[i].data_ptr()), exp_avgs[i].data_ptr(),
-                    exp_avg_sqs[i].data_ptr(), reinterpret_cast<void*>((uintptr_t)ordinals[i]),
-                    reinterpret_cast<void*>((uintptr_t)offsets[i])});
-    numels.push_back(params[i].numel());
-    for (int q = 0; q < 4; ++q) vec = vec && aligned16(ptrs.back()[q]);
-  }
-  const double bc1 = 1.0 - std::pow(beta1, (double)step);
-  const double bc2 = 1.0 - std::pow(beta2, (double)step);
-  const float* gs = scale_ptr(grad_scale);
-  auto launch = [&](auto k) {
-    for_each_table<6>(ptrs, numels, [&](const SegTable<6>& t, int32_t nb) {
-      hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t, (float)lr, (float)beta1, (float)beta2,
-                         (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)bc1, (float)std::sqrt(bc2), decoupled, maximize, gs,
-                         (unsigned long long)seed, (uint32_t)step);
-      XDDP_HIP_CHECK(hipGetLastError());
-    });
-  };
-  switch (gt) {
-    case at::kFloat: launch(vec ? adam_sr_kernel<float, true> : adam_sr_kernel<float, false>); break;
-    case at::kBFloat16: launch(vec ? adam_sr_kernel<bf16_t, true> : adam_sr_kernel<bf16_t, false>); break;
-    case at::kHalf: launch(vec ? adam_sr_kernel<f16_t, true> : adam_sr_kernel<f16_t, false>); break;
-    default: TORCH_CHECK(false, "fused Adam (stochastic rounding): unsupported gradient dtype ", gt);
-  }
-}
-
 }  // namespace kernels
 }  // namespace xddp
+

@@ -321,55 +321,44 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
             with torch.enable_grad():
                 loss = closure()
         self._refuse_capture()
-        C = load()
         for group in self.param_groups:
-            if group["state_bits"] == 8:
-                items = [(p, p.grad, 0, p.numel()) for p in group["params"] if p.grad is not None]
-                for p, *_ in items:
-                    self._init_state(p, group)["step"] += 1
-                self._step8(group, items, grad_scale)
-                continue
-            buckets = defaultdict(lambda: ([], [], [], [], [], []))
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                if "step" not in st:
-                    st["step"] = 0
-                    st["exp_avg"] = _dense_like(p).zero_()
-                    st["exp_avg_sq"] = _dense_like(p).zero_()
-                    if group["master_weights"] and p.dtype in (torch.bfloat16, torch.float16):
-                        st["master"] = p.detach().float().clone(memory_format=torch.preserve_format)
-                st["step"] += 1
-                sr = self._stochastic(p, group)
-                key = _group_key(p, p.grad) + (st["step"], "master" in st, sr)
-                b = buckets[key]
-                b[0].append(p)
-                b[1].append(p.grad)
-                b[2].append(st["exp_avg"])
-                b[3].append(st["exp_avg_sq"])
-                if "master" in st:
-                    b[4].append(st["master"])
-                if sr:
-                    b[5].append((self._ordinal(p), 0))
-            for key, lists in buckets.items():
-                self._launch32(C, group, key, lists, grad_scale)
+            # create state and bump the step of every parameter with a gradient, then update whole parameters
+            items = [(p, p.grad, 0, p.numel()) for p in group["params"] if p.grad is not None]
+            for p, *_ in items:
+                self._init_state(p, group)["step"] += 1
+            (self._step8 if group["state_bits"] == 8 else self._step32)(group, items, grad_scale)
         return loss
 
-    def _launch32(self, C, group, key, lists, grad_scale):
-        """One bucket of the 32-bit states: ``lists`` = (params, grads, exp_avgs, exp_avg_sqs, masters,
-        [(ordinal, element offset)] of the stochastically rounded parameters or ranges)."""
-        (dev, pdt, gdt, step, has_master, sr), (ps, gs, m1, m2, masters, keys) = key, lists
+    def _step32(self, group, ranges, grad_scale):
+        """fp32 states: update ``ranges`` = ``[(param, grad, lo, hi)]`` with each parameter's current step
+        count, one launch per (device, dtypes, step, master, rounding)."""
         b1, b2 = group["betas"]
-        if dev.type != "cuda":
-            self._cpu_step(ps, gs, m1, m2, masters, group, step, grad_scale, keys if sr else None)
-        elif sr:
-            C.fused_adam_sr(ps, gs, m1, m2, [o for o, _ in keys], [e for _, e in keys], group["lr"], b1, b2,
-                            group["eps"], group["weight_decay"], step, group["seed"], self._decoupled,
-                            group["maximize"], grad_scale)
-        else:
-            C.fused_adam(ps, gs, m1, m2, masters, group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                         step, self._decoupled, group["maximize"], grad_scale)
+        # params, grads, exp_avgs, exp_avg_sqs, masters, (ordinal, element offset) of a stochastically rounded range
+        buckets = defaultdict(lambda: ([], [], [], [], [], []))
+        for p, g, lo, hi in ranges:
+            st = self.state[p]
+            sr = self._stochastic(p, group)
+            b = buckets[_group_key(p, g) + (st["step"], "master" in st, sr)]
+            whole = lo == 0 and hi == p.numel()
+            cut = (lambda t: t) if whole else (lambda t: _flat_range(t, lo, hi))
+            b[0].append(cut(p))
+            b[1].append(cut(g))
+            b[2].append(cut(st["exp_avg"]))
+            b[3].append(cut(st["exp_avg_sq"]))
+            if "master" in st:
+                b[4].append(cut(st["master"]))
+            if sr:
+                b[5].append((self._ordinal(p), lo))
+        for (dev, pdt, gdt, step, has_master, sr), (ps, gs, m1, m2, masters, keys) in buckets.items():
+            if dev.type != "cuda":
+                self._cpu_step(ps, gs, m1, m2, masters, group, step, grad_scale, keys if sr else None)
+            elif sr:
+                load().fused_adam_sr(ps, gs, m1, m2, [o for o, _ in keys], [e for _, e in keys], group["lr"], b1, b2,
+                                     group["eps"], group["weight_decay"], step, group["seed"], self._decoupled,
+                                     group["maximize"], grad_scale)
+            else:
+                load().fused_adam(ps, gs, m1, m2, masters, group["lr"], b1, b2, group["eps"], group["weight_decay"],
+                                  step, self._decoupled, group["maximize"], grad_scale)
 
     def _stochastic(self, p, group) -> bool:
         """Whether ``p`` is written with stochastic rounding (bf16 parameters of a
@@ -431,21 +420,20 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
 
     def _init_state(self, p, group):
         st = self.state[p]
-        if "step" not in st and group["state_bits"] == 8:
+        if "step" in st:
+            return st
+        if group["state_bits"] == 8:
             _flat_range(p, 0, p.numel())  # (raises for a parameter that is not dense)
             ng = (p.numel() + _QGROUP - 1) // _QGROUP
-            st["step"] = 0
-            for name in ("exp_avg", "exp_avg_sq"):
+        st["step"] = 0
+        for name in ("exp_avg", "exp_avg_sq"):
+            if group["state_bits"] == 8:
                 st[name + "_q"] = torch.zeros(p.numel(), dtype=torch.uint8, device=p.device)
                 st[name + "_scale"] = torch.zeros(ng, dtype=torch.float32, device=p.device)
-            if group["master_weights"] and p.dtype in (torch.bfloat16, torch.float16):
-                st["master"] = p.detach().float().clone(memory_format=torch.preserve_format)
-        if "step" not in st:
-            st["step"] = 0
-            st["exp_avg"] = _dense_like(p).zero_()
-            st["exp_avg_sq"] = _dense_like(p).zero_()
-            if group["master_weights"] and p.dtype in (torch.bfloat16, torch.float16):
-                st["master"] = p.detach().float().clone(memory_format=torch.preserve_format)
+            else:
+                st[name] = _dense_like(p).zero_()
+        if group["master_weights"] and p.dtype in (torch.bfloat16, torch.float16):
+            st["master"] = p.detach().float().clone(memory_format=torch.preserve_format)
         return st
 
     @torch.no_grad()
@@ -483,7 +471,6 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
         when ``hi == numel``: every group is updated by the piece that delivers its last element.
         The result is still bitwise that of the whole-parameter update."""
         self._refuse_capture()
-        C = load()
         per_group = defaultdict(list)
         for p, g, lo, hi in pieces:
             gi = self._group_index(p)
@@ -506,25 +493,10 @@ class FusedAdamW(_KeepStateDtypes, Optimizer):
                         ranges.append((p, g, lo, hi))
                 self._step8(group, ranges, None)
                 continue
-            buckets = defaultdict(lambda: ([], [], [], [], [], []))
-            for p, g, lo, hi in items:
-                st = self._init_state(p, group)
-                if st["step"] == 0:
+            for p, *_ in items:
+                if self._init_state(p, group)["step"] == 0:
                     raise RuntimeError("step_slices before advance() for this step")
-                sr = self._stochastic(p, group)
-                b = buckets[_group_key(p, g) + (st["step"], "master" in st, sr)]
-                whole = lo == 0 and hi == p.numel()
-                cut = (lambda t: t) if whole else (lambda t: _flat_range(t, lo, hi))
-                b[0].append(cut(p))
-                b[1].append(cut(g))
-                b[2].append(cut(st["exp_avg"]))
-                b[3].append(cut(st["exp_avg_sq"]))
-                if "master" in st:
-                    b[4].append(cut(st["master"]))
-                if sr:
-                    b[5].append((self._ordinal(p), lo))
-            for key, lists in buckets.items():
-                self._launch32(C, group, key, lists, None)
+            self._step32(group, items, None)
 
     def _step8(self, group, ranges, grad_scale):
         """8-bit states: update ``ranges`` = ``[(param, grad, lo, hi)]``, ``lo`` a multiple of 128 and

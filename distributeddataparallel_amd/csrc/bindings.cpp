@@ -5,7 +5,10 @@
 #include <pybind11/stl.h>
 #include <torch/extension.h>
 
+#include <algorithm>
+
 #include "comm/comm.h"
+#include "common.h"
 #include "comm/peer.h"
 #include "kernels/multi_tensor.h"
 #include "kernels/norm.h"
@@ -468,6 +471,56 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       py::arg("offsets"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
       py::arg("weight_decay"), py::arg("step"), py::arg("seed"), py::arg("decoupled"), py::arg("maximize"),
       py::arg("grad_scale") = py::none());
+  m.def("fused_lamb", [](const std::vector<at::Tensor>& p, const std::vector<at::Tensor>& g,
+                         const std::vector<at::Tensor>& m1, const std::vector<at::Tensor>& m2,
+                         const std::vector<at::Tensor>& masters, double lr, double b1, double b2, double eps,
+                         double wd, int64_t step, bool bias_correction, bool adapt, bool maximize,
+                         c10::optional<at::Tensor> gs) {
+        TORCH_CHECK(!p.empty(), "fused_lamb: empty parameter list");
+        return kernels::fused_lamb(p, g, m1, m2, masters, lr, b1, b2, eps, wd, step, bias_correction, adapt, maximize,
+                                   gs, stream_of(p[0]));
+      }, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"), py::arg("exp_avg_sqs"), py::arg("masters"),
+      py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"), py::arg("step"),
+      py::arg("bias_correction"), py::arg("adapt"), py::arg("maximize"), py::arg("grad_scale") = py::none(),
+      "LAMB over a tensor list; returns the per-tensor trust ratios (fp32 [N], on the device)");
+  m.def("fused_lars", [](const std::vector<at::Tensor>& p, const std::vector<at::Tensor>& g,
+                         const std::vector<at::Tensor>& b, const std::vector<at::Tensor>& masters, double lr,
+                         double momentum, double dampening, double wd, bool nesterov, bool maximize, bool first,
+                         double trust_coefficient, double eps, c10::optional<at::Tensor> gs) {
+        TORCH_CHECK(!p.empty(), "fused_lars: empty parameter list");
+        return kernels::fused_lars(p, g, b, masters, lr, momentum, dampening, wd, nesterov, maximize, first,
+                                   trust_coefficient, eps, gs, stream_of(p[0]));
+      }, py::arg("params"), py::arg("grads"), py::arg("momentum_bufs"), py::arg("masters"), py::arg("lr"),
+      py::arg("momentum"), py::arg("dampening"), py::arg("weight_decay"), py::arg("nesterov"), py::arg("maximize"),
+      py::arg("first_step"), py::arg("trust_coefficient"), py::arg("eps"), py::arg("grad_scale") = py::none(),
+      "LARS over a tensor list; returns the per-tensor trust ratios (fp32 [N], on the device)");
+
+  // Topology of a captured HIP graph (hipGraph_t as an integer, e.g. torch.cuda.CUDAGraph(keep_graph=True)
+  // .raw_cuda_graph()): (hipGraphNodeType of every node, edges as (from, to) node indices). Lets a test
+  // assert that captured work is a serial chain of kernel nodes.
+  m.def("hip_graph_topology", [](uintptr_t handle) {
+        hipGraph_t graph = reinterpret_cast<hipGraph_t>(handle);
+        TORCH_CHECK(graph != nullptr, "hip_graph_topology: null graph");
+        size_t nn = 0, ne = 0;
+        XDDP_HIP_CHECK(hipGraphGetNodes(graph, nullptr, &nn));
+        std::vector<hipGraphNode_t> nodes(nn);
+        if (nn) XDDP_HIP_CHECK(hipGraphGetNodes(graph, nodes.data(), &nn));
+        XDDP_HIP_CHECK(hipGraphGetEdges(graph, nullptr, nullptr, &ne));
+        std::vector<hipGraphNode_t> from(ne), to(ne);
+        if (ne) XDDP_HIP_CHECK(hipGraphGetEdges(graph, from.data(), to.data(), &ne));
+        std::vector<int> types(nn);
+        for (size_t i = 0; i < nn; ++i) {
+          hipGraphNodeType t;
+          XDDP_HIP_CHECK(hipGraphNodeGetType(nodes[i], &t));
+          types[i] = (int)t;
+        }
+        auto index = [&](hipGraphNode_t n) {
+          return (int)(std::find(nodes.begin(), nodes.end(), n) - nodes.begin());
+        };
+        std::vector<std::pair<int, int>> edges(ne);
+        for (size_t i = 0; i < ne; ++i) edges[i] = {index(from[i]), index(to[i])};
+        return std::make_pair(types, edges);
+      }, py::arg("graph"), "(node types, (from, to) edges) of a hipGraph_t given as an integer");
 
   kernels::bind_norm_kernels(m);
 }

@@ -92,5 +92,28 @@ void fused_adam_sr(const std::vector<at::Tensor>& params, const std::vector<at::
                    double beta2, double eps, double weight_decay, int64_t step, int64_t seed, bool decoupled,
                    bool maximize, const c10::optional<at::Tensor>& grad_scale, hipStream_t stream);
 
+// Layer-wise trust-ratio optimizers. Both return the fp32 [N] device tensor of the step's per-tensor
+// ratios (1 for a zero-numel tensor, and where a norm is exactly zero; a non-finite norm is not
+// masked). All norms are L2 over one whole tensor, of w = the fp32 master (if `masters` is
+// non-empty; the parameter then receives the rounded master) or the parameter. Three stream-ordered
+// launches per segment table, no host synchronisation; scratch comes from at::empty.
+//
+// LAMB: m, v as Adam on g' = g * grad_scale * (maximize ? -1 : 1);
+//   u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + weight_decay * w   (bc = 1 without bias_correction)
+//   w -= lr * r * u,  r = |w| / |u| if `adapt`, else 1.
+at::Tensor fused_lamb(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                      const std::vector<at::Tensor>& exp_avgs, const std::vector<at::Tensor>& exp_avg_sqs,
+                      const std::vector<at::Tensor>& masters, double lr, double beta1, double beta2, double eps,
+                      double weight_decay, int64_t step, bool bias_correction, bool adapt, bool maximize,
+                      const c10::optional<at::Tensor>& grad_scale, hipStream_t stream);
+
+// LARS: lam = trust_coefficient * |w| / (|g'| + weight_decay * |w| + eps), then torch.optim.SGD on
+// d = lam * (g' + weight_decay * w). |g'| is |grad_scale| * |g|.
+at::Tensor fused_lars(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                      const std::vector<at::Tensor>& momentum_bufs, const std::vector<at::Tensor>& masters, double lr,
+                      double momentum, double dampening, double weight_decay, bool nesterov, bool maximize,
+                      bool first_step, double trust_coefficient, double eps,
+                      const c10::optional<at::Tensor>& grad_scale, hipStream_t stream);
+
 }  // namespace kernels
 }  // namespace xddp

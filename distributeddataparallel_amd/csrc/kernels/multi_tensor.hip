@@ -593,9 +593,12 @@ struct SgdUpdate {
   const float gscale;
   __device__ __forceinline__ explicit SgdUpdate(const SgdArgs& a_)
       : a(a_), gscale((a_.gs ? *a_.gs : 1.f) * (a_.maximize ? -1.f : 1.f)) {}
-  __device__ __forceinline__ void operator()(float& pv, float gv, float& bv) const {
+  // LW (layer-wise, LARS): g' + wd w is multiplied by the tensor's trust ratio `lam` first
+  template <bool LW = false>
+  __device__ __forceinline__ void operator()(float& pv, float gv, float& bv, float lam = 1.f) const {
     float d = gv * gscale;
     if (a.wd != 0.f) d = fmaf(a.wd, pv, d);
+    if (LW) d *= lam;
     if (MOM) {
       bv = a.first ? d : fmaf(a.momentum, bv, (1.f - a.dampening) * d);
       d = a.nesterov ? fmaf(a.momentum, bv, d) : bv;
@@ -606,10 +609,13 @@ struct SgdUpdate {
 
 // MASTER: the update reads and writes the fp32 master, and the updated master is rounded into the
 // model's param (of type P) in the same pass (no second launch that re-reads the masters).
-template <typename P, typename G, bool VEC, bool MOM, bool MASTER>
-__global__ __launch_bounds__(kThreads) void sgd_kernel(SegTable<MASTER ? 4 : 3> t, SgdArgs a) {
+// LW: one more slot, the last, holds the address of the tensor's trust ratio (fused_lars).
+template <typename P, typename G, bool VEC, bool MOM, bool MASTER, bool LW = false>
+__global__ __launch_bounds__(kThreads) void sgd_kernel(SegTable<(MASTER ? 4 : 3) + (LW ? 1 : 0)> t, SgdArgs a) {
   using W = std::conditional_t<MASTER, float, P>;  // what the update reads and writes
   const Chunk c = block_chunk(t);
+  float lam = 1.f;
+  if constexpr (LW) lam = *reinterpret_cast<const float*>(t.ptr[MASTER ? 4 : 3][c.s]);
   W* p = reinterpret_cast<W*>(t.ptr[0][c.s]);
   const G* g = reinterpret_cast<const G*>(t.ptr[1][c.s]);
   float* buf = reinterpret_cast<float*>(t.ptr[2][c.s]);
@@ -626,7 +632,7 @@ __global__ __launch_bounds__(kThreads) void sgd_kernel(SegTable<MASTER ? 4 : 3> 
       Vec8<G>::ld(g + i, gv);
       if (MOM && !a.first) Vec8<float>::ld(buf + i, bv);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) upd(pv[j], gv[j], bv[j]);
+      for (int j = 0; j < 8; ++j) upd.template operator()<LW>(pv[j], gv[j], bv[j], lam);
       Vec8<W>::st(p + i, pv);
       if (MOM) Vec8<float>::st(buf + i, bv);
       if (MASTER) Vec8<P>::st(q + i, pv);
@@ -634,7 +640,7 @@ __global__ __launch_bounds__(kThreads) void sgd_kernel(SegTable<MASTER ? 4 : 3> 
       for (int64_t k = i; k < i + 8 && k < n; ++k) {
         float pv = Elem<W, float>::ld(p, k), gv = Elem<G, float>::ld(g, k), bv = 0.f;
         if (MOM && !a.first) bv = buf[k];
-        upd(pv, gv, bv);
+        upd.template operator()<LW>(pv, gv, bv, lam);
         Elem<W, float>::st(p, k, pv);
         if (MOM) buf[k] = bv;
         if (MASTER) Elem<P, float>::st(q, k, pv);
@@ -1318,6 +1324,380 @@ void stochastic_round_bf16(const at::Tensor& x, const at::Tensor& out, int64_t s
                      reinterpret_cast<bf16_t*>(out.data_ptr()), n, (unsigned long long)seed,
                      (unsigned long long)ordinal, (uint32_t)step, offset);
   XDDP_HIP_CHECK(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------
+// Layer-wise trust-ratio optimizers: LAMB and LARS. Both need the L2 norm of whole tensors before
+// any element of them is updated, so a step is three stream-ordered launches (per segment table):
+//   1. a pass that writes two sums of squares per 8192-element chunk, at the chunk's index in the
+//      whole list. A tensor is never split across segment tables, but a list of more than 40
+//      tensors is, so partials and ratios are indexed over the list, not over one launch;
+//   2. trust_ratio_kernel: one wave per tensor folds that tensor's chunk partials in a fixed order
+//      and writes its ratio;
+//   3. the update, which reads the ratio through a pointer slot of the segment table.
+// A chunk partial depends on its own 8192 elements only and the fold on one tensor's partials only,
+// so a tensor's result is bitwise the same alone, in any list, and on every replica.
+// ------------------------------------------------------------------------------------
+struct TrustArgs {
+  bool lars;   // false: LAMB, ratio = |w| / |u|; true: LARS, ratio = tc |w| / (|g'| + wd |w| + eps)
+  bool adapt;  // LAMB: false gives ratio 1
+  float tc, wd, eps;
+  const float* gs;  // LARS: |g'| = |*gs| |g|
+};
+
+// Slots {this tensor's chunk partials (pairs of floats), the address of its ratio}; "numel" is the
+// tensor's chunk count (0 for a zero-numel tensor: ratio 1). Block s is tensor s. A norm that is
+// exactly zero gives ratio 1; a non-finite one is not masked.
+__global__ __launch_bounds__(64) void trust_ratio_kernel(SegTable<2> t, TrustArgs a) {
+  const int s = blockIdx.x;
+  const float* part = reinterpret_cast<const float*>(t.ptr[0][s]);
+  const int64_t n = t.numel[s];
+  double s0 = 0.0, s1 = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 64) {
+    s0 += (double)part[2 * i];
+    s1 += (double)part[2 * i + 1];
+  }
+  s0 = dev::wave_sum(s0);
+  s1 = dev::wave_sum(s1);
+  if (threadIdx.x != 0) return;
+  const double wn = sqrt(s0);
+  double r = 1.0;
+  if (a.lars) {
+    const double gn = sqrt(s1) * fabs(a.gs ? (double)*a.gs : 1.0);
+    if (wn != 0.0 && gn != 0.0) r = (double)a.tc * wn / (gn + (double)a.wd * wn + (double)a.eps);
+  } else {
+    const double un = sqrt(s1);
+    if (a.adapt && wn != 0.0 && un != 0.0) r = wn / un;
+  }
+  *reinterpret_cast<float*>(t.ptr[1][s]) = (float)r;
+}
+
+// Chunk layout of a list: tensor i's partials start at pair index start[i]
+struct ChunkMap {
+  std::vector<int64_t> start, count;
+  int64_t total = 0;
+  explicit ChunkMap(const std::vector<at::Tensor>& ts) {
+    for (auto& x : ts) {
+      start.push_back(total);
+      count.push_back((x.numel() + kChunk - 1) / kChunk);
+      total += count.back();
+    }
+  }
+};
+
+static void launch_trust_ratio(float* partials, float* ratios, const ChunkMap& cm, const TrustArgs& a,
+                               hipStream_t stream) {
+  SegTable<2> t;
+  t.nseg = 0;
+  auto flush = [&]() {
+    hipLaunchKernelGGL(trust_ratio_kernel, dim3(t.nseg), dim3(64), 0, stream, t, a);
+    XDDP_HIP_CHECK(hipGetLastError());
+    t.nseg = 0;
+  };
+  for (size_t i = 0; i < cm.start.size(); ++i) {
+    t.ptr[0][t.nseg] = partials + 2 * cm.start[i];
+    t.ptr[1][t.nseg] = ratios + i;
+    t.numel[t.nseg] = cm.count[i];
+    t.blk_end[t.nseg] = t.nseg + 1;
+    if (++t.nseg == kMaxSeg) flush();
+  }
+  if (t.nseg) flush();
+}
+
+// ---- LAMB ---------------------------------------------------------------------------
+struct LambArgs {
+  float lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2_sqrt;
+  bool maximize;
+  const float* gs;
+};
+
+// The update direction u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + wd w. Stage 1 takes its norm
+// and stage 3 applies it: both call this one function, compiled without contraction (the one FMA
+// is explicit), so the norm is exactly the norm of what is applied.
+__device__ __forceinline__ float lamb_dir(const LambArgs& a, float w, float m, float v) {
+#pragma clang fp contract(off)
+  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
+  const float q = (m / a.bc1) / denom;
+  return a.wd != 0.f ? fmaf(a.wd, w, q) : q;
+}
+
+// Stage 1, slots {w (the fp32 master, or the parameter), grad, exp_avg, exp_avg_sq, this tensor's
+// chunk partials}: updates the moments, forms u in registers and writes sum(w^2), sum(u^2) of the chunk.
+struct LambMoments {
+  const LambArgs& a;
+  const float gscale;
+  float sw = 0.f, su = 0.f;
+  __device__ __forceinline__ explicit LambMoments(const LambArgs& a_)
+      : a(a_), gscale((a_.gs ? *a_.gs : 1.f) * (a_.maximize ? -1.f : 1.f)) {}
+  __device__ __forceinline__ void operator()(float wv, float gv, float& mv, float& vv) {
+    const float gg = gv * gscale;
+    mv = fmaf(a.b1, mv, a.omb1 * gg);
+    vv = fmaf(a.b2, vv, a.omb2 * gg * gg);
+    const float u = lamb_dir(a, wv, mv, vv);
+    sw = fmaf(wv, wv, sw);
+    su = fmaf(u, u, su);
+  }
+};
+
+template <typename W, typename G, bool VEC>
+__global__ __launch_bounds__(kThreads) void lamb_moments_kernel(SegTable<5> t, LambArgs a) {
+  __shared__ float scratch[kThreads / 64];
+  const Chunk c = block_chunk(t);
+  const W* w = reinterpret_cast<const W*>(t.ptr[0][c.s]);
+  const G* g = reinterpret_cast<const G*>(t.ptr[1][c.s]);
+  float* m = reinterpret_cast<float*>(t.ptr[2][c.s]);
+  float* v = reinterpret_cast<float*>(t.ptr[3][c.s]);
+  float* part = reinterpret_cast<float*>(t.ptr[4][c.s]) + 2 * (c.base / kChunk);
+  const int64_t n = c.n;
+  LambMoments upd(a);
+  if (VEC && c.base + kChunk <= n) {  // whole chunk: every load first (see adam_kernel)
+    float wv[kIters][8], gv[kIters][8], mv[kIters][8], vv[kIters][8];
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int64_t i = c.base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+      Vec8<W>::ld(w + i, wv[it]);
+      Vec8<G>::ld(g + i, gv[it]);
+      Vec8<float>::ld(m + i, mv[it]);
+      Vec8<float>::ld(v + i, vv[it]);
+    }
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int64_t i = c.base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) upd(wv[it][j], gv[it][j], mv[it][j], vv[it][j]);
+      Vec8<float>::st(m + i, mv[it]);
+      Vec8<float>::st(v + i, vv[it]);
+    }
+  } else {
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int64_t i = c.base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+      if (VEC && i + 8 <= n) {
+        float wv[8], gv[8], mv[8], vv[8];
+        Vec8<W>::ld(w + i, wv);
+        Vec8<G>::ld(g + i, gv);
+        Vec8<float>::ld(m + i, mv);
+        Vec8<float>::ld(v + i, vv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) upd(wv[j], gv[j], mv[j], vv[j]);
+        Vec8<float>::st(m + i, mv);
+        Vec8<float>::st(v + i, vv);
+      } else {
+        for (int64_t k = i; k < i + 8 && k < n; ++k) {
+          float mv = m[k], vv = v[k];
+          upd(Elem<W, float>::ld(w, k), Elem<G, float>::ld(g, k), mv, vv);
+          m[k] = mv;
+          v[k] = vv;
+        }
+      }
+    }
+  }
+  const float sw = dev::block_sum(upd.sw, scratch);
+  const float su = dev::block_sum(upd.su, scratch);
+  if (threadIdx.x == 0) {
+    part[0] = sw;
+    part[1] = su;
+  }
+}
+
+// Stage 3, slots {w (the fp32 master, or the parameter), exp_avg, exp_avg_sq, the address of the
+// tensor's ratio, the model's parameter (MASTER)}: w <- w - lr r u, u recomputed from the stored moments.
+template <typename P, bool VEC, bool MASTER>
+__global__ __launch_bounds__(kThreads) void lamb_apply_kernel(SegTable<5> t, LambArgs a) {
+  using W = std::conditional_t<MASTER, float, P>;
+  const Chunk c = block_chunk(t);
+  W* w = reinterpret_cast<W*>(t.ptr[0][c.s]);
+  const float* m = reinterpret_cast<const float*>(t.ptr[1][c.s]);
+  const float* v = reinterpret_cast<const float*>(t.ptr[2][c.s]);
+  const float step = -a.lr * *reinterpret_cast<const float*>(t.ptr[3][c.s]);
+  P* q = nullptr;
+  if constexpr (MASTER) q = reinterpret_cast<P*>(t.ptr[4][c.s]);
+  const int64_t n = c.n;
+#pragma unroll
+  for (int it = 0; it < kIters; ++it) {
+    const int64_t i = c.base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+    if (VEC && i + 8 <= n) {
+      float wv[8], mv[8], vv[8];
+      Vec8<W>::ld(w + i, wv);
+      Vec8<float>::ld(m + i, mv);
+      Vec8<float>::ld(v + i, vv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) wv[j] = fmaf(step, lamb_dir(a, wv[j], mv[j], vv[j]), wv[j]);
+      Vec8<W>::st(w + i, wv);
+      if (MASTER) Vec8<P>::st(q + i, wv);
+    } else {
+      for (int64_t k = i; k < i + 8 && k < n; ++k) {
+        float wv = Elem<W, float>::ld(w, k);
+        wv = fmaf(step, lamb_dir(a, wv, m[k], v[k]), wv);
+        Elem<W, float>::st(w, k, wv);
+        if (MASTER) Elem<P, float>::st(q, k, wv);
+      }
+    }
+  }
+}
+
+at::Tensor fused_lamb(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                      const std::vector<at::Tensor>& exp_avgs, const std::vector<at::Tensor>& exp_avg_sqs,
+                      const std::vector<at::Tensor>& masters, double lr, double beta1, double beta2, double eps,
+                      double weight_decay, int64_t step, bool bias_correction, bool adapt, bool maximize,
+                      const c10::optional<at::Tensor>& grad_scale, hipStream_t stream) {
+  const size_t N = params.size();
+  TORCH_CHECK(N > 0, "lamb: empty tensor list");
+  TORCH_CHECK(grads.size() == N && exp_avgs.size() == N && exp_avg_sqs.size() == N, "lamb: list length mismatch");
+  const bool has_master = !masters.empty();
+  TORCH_CHECK(!has_master || masters.size() == N, "lamb: masters length mismatch");
+  TORCH_CHECK(step >= 1, "lamb: step must be >= 1");
+  const auto pt = params[0].scalar_type(), gt = grads[0].scalar_type();
+  TORCH_CHECK(pt != at::kDouble && gt != at::kDouble, "fused LAMB: fp64 unsupported");
+  TORCH_CHECK(!has_master || pt == at::kBFloat16 || pt == at::kHalf, "master-weight LAMB: model params must be bf16/fp16");
+  check_adam_lists("lamb", params, grads, {&exp_avgs, &exp_avg_sqs}, masters, nullptr, nullptr);
+  const ChunkMap cm(params);
+  const auto f32 = at::TensorOptions().dtype(at::kFloat).device(params[0].device());
+  at::Tensor partials = at::empty({2 * std::max<int64_t>(cm.total, 1)}, f32);
+  at::Tensor ratios = at::empty({(int64_t)N}, f32);
+  float* part = partials.data_ptr<float>();
+  float* rat = ratios.data_ptr<float>();
+  std::vector<std::array<void*, 5>> p1, p3;
+  std::vector<int64_t> numels;
+  bool vec1 = true, vec3 = true;
+  for (size_t i = 0; i < N; ++i) {
+    void* w = has_master ? masters[i].data_ptr() : params[i].data_ptr();
+    p1.push_back({w, const_cast<void*>(grads[i].data_ptr()), exp_avgs[i].data_ptr(), exp_avg_sqs[i].data_ptr(),
+                  part + 2 * cm.start[i]});
+    p3.push_back({w, exp_avgs[i].data_ptr(), exp_avg_sqs[i].data_ptr(), rat + i,
+                  has_master ? params[i].data_ptr() : nullptr});
+    numels.push_back(params[i].numel());
+    for (int q = 0; q < 4; ++q) vec1 = vec1 && aligned16(p1.back()[q]);
+    vec3 = vec3 && aligned16(w) && aligned16(p3.back()[1]) && aligned16(p3.back()[2]) && aligned16(p3.back()[4]);
+  }
+  const double bc1 = bias_correction ? 1.0 - std::pow(beta1, (double)step) : 1.0;
+  const double bc2 = bias_correction ? 1.0 - std::pow(beta2, (double)step) : 1.0;
+  const LambArgs args = {(float)lr,  (float)beta1,        (float)beta2, (float)(1.0 - beta1),  (float)(1.0 - beta2),
+                         (float)eps, (float)weight_decay, (float)bc1,   (float)std::sqrt(bc2), maximize,
+                         scale_ptr(grad_scale)};
+  const auto wt = has_master ? at::kFloat : pt;
+  XDDP_DISPATCH_FLOAT_NO_F64(wt, W, "fused LAMB: unsupported parameter dtype ",
+    XDDP_DISPATCH_FLOAT_NO_F64(gt, G, "fused LAMB: unsupported gradient dtype ", {
+      launch_list<5>(vec1 ? lamb_moments_kernel<W, G, true> : lamb_moments_kernel<W, G, false>, p1, numels, args, stream);
+    }));
+  launch_trust_ratio(part, rat, cm, TrustArgs{false, adapt, 0.f, 0.f, 0.f, nullptr}, stream);
+  XDDP_DISPATCH_FLOAT_NO_F64(pt, P, "fused LAMB: unsupported parameter dtype ", {
+    if (has_master) {
+      if constexpr (!std::is_same<P, float>::value)
+        launch_list<5>(vec3 ? lamb_apply_kernel<P, true, true> : lamb_apply_kernel<P, false, true>, p3, numels, args, stream);
+    } else {
+      launch_list<5>(vec3 ? lamb_apply_kernel<P, true, false> : lamb_apply_kernel<P, false, false>, p3, numels, args, stream);
+    }
+  });
+  return ratios;
+}
+
+// ---- LARS ---------------------------------------------------------------------------
+// Slots {w, grad, this tensor's chunk partials}: sum(w^2), sum(g^2) of the chunk (g unscaled:
+// the finalize multiplies its norm by |grad_scale| once).
+template <typename W, typename G, bool VEC>
+__global__ __launch_bounds__(kThreads) void sumsq2_kernel(SegTable<3> t) {
+  __shared__ float scratch[kThreads / 64];
+  const Chunk c = block_chunk(t);
+  const W* w = reinterpret_cast<const W*>(t.ptr[0][c.s]);
+  const G* g = reinterpret_cast<const G*>(t.ptr[1][c.s]);
+  float* part = reinterpret_cast<float*>(t.ptr[2][c.s]) + 2 * (c.base / kChunk);
+  const int64_t n = c.n;
+  float sw = 0.f, sg = 0.f;
+#pragma unroll
+  for (int it = 0; it < kIters; ++it) {
+    const int64_t i = c.base + ((int64_t)it * kThreads + threadIdx.x) * 8;
+    if (VEC && i + 8 <= n) {
+      float wv[8], gv[8];
+      Vec8<W>::ld(w + i, wv);
+      Vec8<G>::ld(g + i, gv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        sw = fmaf(wv[j], wv[j], sw);
+        sg = fmaf(gv[j], gv[j], sg);
+      }
+    } else {
+      for (int64_t k = i; k < i + 8 && k < n; ++k) {
+        const float wv = Elem<W, float>::ld(w, k), gv = Elem<G, float>::ld(g, k);
+        sw = fmaf(wv, wv, sw);
+        sg = fmaf(gv, gv, sg);
+      }
+    }
+  }
+  sw = dev::block_sum(sw, scratch);
+  sg = dev::block_sum(sg, scratch);
+  if (threadIdx.x == 0) {
+    part[0] = sw;
+    part[1] = sg;
+  }
+}
+
+at::Tensor fused_lars(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                      const std::vector<at::Tensor>& momentum_bufs, const std::vector<at::Tensor>& masters, double lr,
+                      double momentum, double dampening, double weight_decay, bool nesterov, bool maximize,
+                      bool first_step, double trust_coefficient, double eps,
+                      const c10::optional<at::Tensor>& grad_scale, hipStream_t stream) {
+  const size_t N = params.size();
+  TORCH_CHECK(N > 0, "lars: empty tensor list");
+  TORCH_CHECK(grads.size() == N, "lars: list length mismatch");
+  const bool mom = momentum != 0.0, has_master = !masters.empty();
+  TORCH_CHECK(!mom || momentum_bufs.size() == N, "lars: momentum buffers missing");
+  TORCH_CHECK(!has_master || masters.size() == N, "lars: masters length mismatch");
+  const auto pt = params[0].scalar_type(), gt = grads[0].scalar_type();
+  TORCH_CHECK(pt != at::kDouble && gt != at::kDouble, "fused LARS: fp64 unsupported");
+  TORCH_CHECK(!has_master || pt == at::kBFloat16 || pt == at::kHalf, "master-weight LARS: model params must be bf16/fp16");
+  if (mom) check_adam_lists("lars", params, grads, {&momentum_bufs}, masters, nullptr, nullptr);
+  else check_adam_lists("lars", params, grads, {}, masters, nullptr, nullptr);
+  const ChunkMap cm(params);
+  const auto f32 = at::TensorOptions().dtype(at::kFloat).device(params[0].device());
+  at::Tensor partials = at::empty({2 * std::max<int64_t>(cm.total, 1)}, f32);
+  at::Tensor ratios = at::empty({(int64_t)N}, f32);
+  float* part = partials.data_ptr<float>();
+  float* rat = ratios.data_ptr<float>();
+  std::vector<std::array<void*, 3>> p1;
+  std::vector<std::array<void*, 4>> p3;   // {param, grad, buf, ratio}
+  std::vector<std::array<void*, 5>> p3m;  // {master, grad, buf, param, ratio}
+  std::vector<int64_t> numels;
+  bool vec1 = true, vec3 = true;
+  for (size_t i = 0; i < N; ++i) {
+    void* w = has_master ? masters[i].data_ptr() : params[i].data_ptr();
+    void* g = const_cast<void*>(grads[i].data_ptr());
+    void* b = mom ? momentum_bufs[i].data_ptr() : nullptr;
+    p1.push_back({w, g, part + 2 * cm.start[i]});
+    if (has_master) p3m.push_back({w, g, b, params[i].data_ptr(), rat + i});
+    else p3.push_back({w, g, b, rat + i});
+    numels.push_back(params[i].numel());
+    vec1 = vec1 && aligned16(w) && aligned16(g);
+    vec3 = vec3 && aligned16(w) && aligned16(g) && aligned16(b) && aligned16(params[i].data_ptr());
+  }
+  const SgdArgs args = sgd_args(lr, momentum, dampening, weight_decay, nesterov, maximize, first_step, grad_scale);
+  const auto wt = has_master ? at::kFloat : pt;
+  XDDP_DISPATCH_FLOAT_NO_F64(wt, W, "fused LARS: unsupported parameter dtype ",
+    XDDP_DISPATCH_FLOAT_NO_F64(gt, G, "fused LARS: unsupported gradient dtype ", {
+      auto k = vec1 ? sumsq2_kernel<W, G, true> : sumsq2_kernel<W, G, false>;
+      for_each_table<3>(p1, numels, [&](const SegTable<3>& t, int32_t nb) {
+        hipLaunchKernelGGL(k, dim3(nb), dim3(kThreads), 0, stream, t);
+        XDDP_HIP_CHECK(hipGetLastError());
+      });
+    }));
+  launch_trust_ratio(part, rat, cm,
+                     TrustArgs{true, true, (float)trust_coefficient, (float)weight_decay, (float)eps,
+                               scale_ptr(grad_scale)},
+                     stream);
+  XDDP_DISPATCH_FLOAT_NO_F64(pt, P, "fused LARS: unsupported parameter dtype ",
+    XDDP_DISPATCH_FLOAT_NO_F64(gt, G, "fused LARS: unsupported gradient dtype ", {
+      if (has_master) {
+        if constexpr (!std::is_same<P, float>::value)
+          launch_list<5>(vec3 ? (mom ? sgd_kernel<P, G, true, true, true, true> : sgd_kernel<P, G, true, false, true, true>)
+                              : (mom ? sgd_kernel<P, G, false, true, true, true> : sgd_kernel<P, G, false, false, true, true>),
+                         p3m, numels, args, stream);
+      } else {
+        launch_list<4>(vec3 ? (mom ? sgd_kernel<P, G, true, true, false, true> : sgd_kernel<P, G, true, false, false, true>)
+                            : (mom ? sgd_kernel<P, G, false, true, false, true> : sgd_kernel<P, G, false, false, false, true>),
+                       p3, numels, args, stream);
+      }
+    }));
+  return ratios;
 }
 
 }  // namespace kernels

@@ -765,8 +765,9 @@ class DistributedDataParallel(nn.Module, Joinable):
         """Run the optimizer update inside backward, bucket by bucket, on a side HIP stream; the
         compute stream waits for the side stream at the end of backward. Do not call
         ``optimizer.step()`` afterwards (the reference's ``_register_fused_optim`` contract,
-        ``pt:nn/parallel/distributed.py:2061-2131``). Needs an optimizer with ``step_params`` /
-        ``advance`` / ``step_slices`` (``FusedAdamW``, ``FusedAdam``).
+        ``pt:nn/parallel/distributed.py:2061-2131``). Needs an optimizer with ``step_params``; the
+        tail schedule also needs ``advance`` / ``step_slices`` (``FusedAdamW``, ``FusedAdam``), which
+        the layer-wise ``FusedLAMB`` / ``FusedLARS`` cannot have (``schedule="backward"`` only).
 
         ``schedule="tail"`` (default) puts the updates where the GPU is otherwise idle — under the
         LAST bucket's all-reduce, which nothing in backward can hide:
@@ -786,11 +787,20 @@ class DistributedDataParallel(nn.Module, Joinable):
         measured no gain (hipBLASLt's backward GEMMs already occupy every CU) and it leaves the
         tail all-reduce exposed.
         """
-        for attr in ("step_params", "advance", "step_slices"):
-            if not hasattr(optimizer, attr):
-                raise TypeError(f"register_overlapped_optimizer needs an optimizer with {attr} (FusedAdamW)")
         if schedule not in ("tail", "backward"):
             raise ValueError(f"unknown overlapped-optimizer schedule {schedule!r} (use 'tail' or 'backward')")
+        name = type(optimizer).__name__
+        if not hasattr(optimizer, "step_params"):
+            raise TypeError(f"register_overlapped_optimizer needs an optimizer with step_params (FusedAdamW, "
+                            f"FusedAdam, FusedLAMB, FusedLARS); {name} has none")
+        if schedule == "tail":
+            for attr in ("advance", "step_slices"):
+                if not hasattr(optimizer, attr):
+                    raise TypeError(
+                        f"register_overlapped_optimizer(schedule='tail') updates the last bucket chunk by chunk and "
+                        f"needs an optimizer with {attr} (FusedAdamW, FusedAdam); {name} has none. A layer-wise "
+                        f"optimizer (FusedLAMB, FusedLARS) needs a whole tensor's norm before it can update any "
+                        f"element of it: use schedule='backward', which steps whole parameters bucket by bucket")
         if tail_chunk_bytes is None:
             tail_chunk_bytes = int(float(os.environ.get("XDDP_TAIL_CHUNK_MB", "64")) * (1 << 20))
         side = torch.cuda.Stream(self._param_device) if self.device_type == "cuda" else None

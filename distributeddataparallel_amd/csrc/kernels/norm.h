@@ -149,6 +149,14 @@ std::vector<at::Tensor> cross_entropy_forward(const at::Tensor& logits, const at
                                               const at::Tensor& bad);
 at::Tensor cross_entropy_backward(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& lse,
                                   const at::Tensor& gscale, int64_t ignore_index);
+// cross_entropy_rows.hip: the same for fp32 / bf16 / fp16 logits of any width and alignment, with
+// label smoothing, z-loss and reduction 0 none | 1 sum | 2 mean (reduced loss and count on the device)
+std::vector<at::Tensor> cross_entropy_rows_forward(const at::Tensor& logits, const at::Tensor& target,
+                                                   int64_t ignore_index, double label_smoothing, double z_loss,
+                                                   int64_t reduction, const at::Tensor& bad);
+at::Tensor cross_entropy_rows_backward(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& lse,
+                                       const at::Tensor& g, const c10::optional<at::Tensor>& count,
+                                       int64_t ignore_index, double label_smoothing, double z_loss);
 
 }  // namespace kernels
 }  // namespace xddp

@@ -1,8 +1,25 @@
-"""Softmax cross-entropy on xddp's HIP kernels (``csrc/kernels/cross_entropy.hip``) for the
-Llama-3-8B LM head of BASELINE.json config 5: bf16 logits [rows, vocab], fp32 math, mean over
-the non-ignored rows — ``F.cross_entropy(logits.float(), target)`` without the 2.1 GB fp32 copy
-of the logits, its zero-filled fp32 gradient and the casts (one read of the logits forward, one
-read + one bf16 write backward). CPU tensors and other dtypes / shapes fall back to torch.
+"""Softmax cross-entropy on xddp's HIP kernels: fp32 math on fp32 / bf16 / fp16 logits
+[rows, classes] without an fp32 copy of the logits, its zero-filled fp32 gradient and the casts
+(one read of the logits forward, one read + one write in the logits' dtype backward).
+
+Two sets of kernels serve it. ``csrc/kernels/cross_entropy.hip`` is the Llama-3-8B LM head of
+BASELINE.json config 5: bf16 logits, a class count divisible by 8, mean over the non-ignored rows;
+a call with default arguments on such logits runs it exactly as before. Every other native call
+runs ``csrc/kernels/cross_entropy_rows.hip``: any class count >= 1 and any row alignment (one wave
+per row up to 1024 classes, the classification heads; one block per row above), label smoothing,
+z-loss and the reductions none / sum / mean, reduced on the device. CPU tensors, other ranks and
+other dtypes fall back to a torch composition with the same semantics.
+
+With ``lse`` the row's log-sum-exp, ``keep = target != ignore_index``, ``eps = label_smoothing`` and
+``z = z_loss``::
+
+    row loss      keep * ((1 - eps) * (lse - x[t]) + eps * (lse - mean(x)) + z * lse**2)
+    row gradient  g_r * keep * (softmax * (1 + 2 * z * lse) - (1 - eps) * onehot(t) - eps / classes)
+
+At ``z = 0`` this is torch's ``label_smoothing``. ``"mean"`` divides by the number of kept rows,
+at least 1: a finite 0 (not torch's NaN) when every row is ignored. A ``-inf`` (masked) logit gets a
+gradient of exactly 0 and leaves the loss finite at ``eps = 0``; at ``eps > 0`` that row's loss is
+``+inf``, as in torch (the smoothing term averages ``-log p`` over every class).
 
 Targets outside ``[0, classes)`` other than ``ignore_index`` are an error, as in torch. The
 kernel makes that row's loss NaN (so the step's loss shows it at once), gives it no gradient and
@@ -24,9 +41,11 @@ import torch.nn.functional as F
 
 from .._native import load
 
-__all__ = ["cross_entropy", "check_targets"]
+__all__ = ["cross_entropy", "CrossEntropyLoss", "check_targets"]
 
 _FLAGS: dict = {}  # device index -> (device flag int32[1], pinned host copy, event of the copy)
+_REDUCTIONS = {"none": 0, "sum": 1, "mean": 2}
+_NATIVE_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
 
 def _flag(dev: torch.device):
@@ -81,11 +100,102 @@ class _CrossEntropy(torch.autograd.Function):
         return d, None, None
 
 
-def cross_entropy(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
-    """Mean softmax cross-entropy of ``logits`` [rows, classes] against ``target`` [rows]; bf16
-    CUDA logits with a class count divisible by 8 run the fused kernels, anything else
-    ``F.cross_entropy`` on the fp32 upcast."""
-    if (logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 2 and logits.size(1) % 8 == 0
-            and target.dtype == torch.long and target.dim() == 1):
+class _CrossEntropyRows(torch.autograd.Function):
+    """cross_entropy_rows.hip: the row kernel and, for sum / mean, the finalize kernel forward (no
+    torch reduction in between), one kernel backward; the kept-row count stays on the device."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, label_smoothing, z_loss, reduction):
+        C = load()
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing:
+            check_targets()
+        flag, host, ev = _flag(logits.device)
+        out = C.cross_entropy_rows_forward(logits, target, ignore_index, label_smoothing, z_loss,
+                                           _REDUCTIONS[reduction], flag)
+        if not capturing:
+            host.copy_(flag, non_blocking=True)
+            ev.record(torch.cuda.current_stream(logits.device))
+            if os.environ.get("XDDP_XENT_CHECK") == "sync":
+                check_targets(block=True)
+        if reduction == "mean":
+            ctx.save_for_backward(logits, target, out[1], out[3])
+        else:
+            ctx.save_for_backward(logits, target, out[1])
+        ctx.args = (ignore_index, label_smoothing, z_loss)
+        return out[0] if reduction == "none" else out[2]
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, lse, *count = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous().reshape(-1)
+        d = load().cross_entropy_rows_backward(logits, target, lse, g, count[0] if count else None, *ctx.args)
+        return d, None, None, None, None, None
+
+
+def _fallback(logits, target, ignore_index, label_smoothing, z_loss, reduction):
+    """The same semantics in plain torch, on the fp32 upcast."""
+    x = logits.float()
+    if label_smoothing == 0.0 and z_loss == 0.0 and reduction == "mean":
+        return F.cross_entropy(x, target, ignore_index=ignore_index)
+    rows = F.cross_entropy(x, target, ignore_index=ignore_index, label_smoothing=label_smoothing, reduction="none")
+    keep = target != ignore_index
+    if z_loss != 0.0:
+        rows = rows + z_loss * torch.logsumexp(x, 1 if x.dim() > 1 else 0) ** 2 * keep
+    if reduction == "none":
+        return rows
+    return rows.sum() if reduction == "sum" else rows.sum() / keep.sum().clamp_min(1)
+
+
+def cross_entropy(logits: torch.Tensor, target: torch.Tensor, ignore_index: int = -100, *,
+                  label_smoothing: float = 0.0, z_loss: float = 0.0, reduction: str = "mean") -> torch.Tensor:
+    """Softmax cross-entropy of ``logits`` [rows, classes] against ``target`` [rows] with label
+    smoothing, z-loss (``z_loss * lse**2`` per row) and ``reduction`` in none / sum / mean (module
+    docstring). 2-D fp32 / bf16 / fp16 CUDA logits with int64 targets run the HIP kernels, anything
+    else the torch composition on the fp32 upcast."""
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"cross_entropy: label_smoothing must be in [0, 1), got {label_smoothing}")
+    if not z_loss >= 0.0:
+        raise ValueError(f"cross_entropy: z_loss must be >= 0, got {z_loss}")
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"cross_entropy: reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
+    default = label_smoothing == 0.0 and z_loss == 0.0 and reduction == "mean"
+    if (default and logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 2
+            and logits.size(1) % 8 == 0 and target.dtype == torch.long and target.dim() == 1):
         return _CrossEntropy.apply(logits.contiguous(), target.contiguous(), ignore_index)
-    return F.cross_entropy(logits.float(), target, ignore_index=ignore_index)
+    if (logits.is_cuda and logits.dtype in _NATIVE_DTYPES and logits.dim() == 2 and logits.size(1) >= 1
+            and target.dtype == torch.long and target.dim() == 1 and target.size(0) == logits.size(0)
+            and target.device == logits.device):
+        logits = logits.contiguous()
+        if logits.data_ptr() % 16:  # a view into the middle of a buffer: the kernels want a 16-B aligned base
+            logits = logits.clone()
+        return _CrossEntropyRows.apply(logits, target.contiguous(), ignore_index, float(label_smoothing),
+                                       float(z_loss), reduction)
+    return _fallback(logits, target, ignore_index, label_smoothing, z_loss, reduction)
+
+
+class CrossEntropyLoss(torch.nn.Module):
+    """:func:`cross_entropy` as a module (``nn.CrossEntropyLoss`` without class weights and
+    probability targets, plus ``z_loss``)."""
+
+    def __init__(self, ignore_index: int = -100, label_smoothing: float = 0.0, z_loss: float = 0.0,
+                 reduction: str = "mean"):
+        super().__init__()
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"CrossEntropyLoss: label_smoothing must be in [0, 1), got {label_smoothing}")
+        if not z_loss >= 0.0:
+            raise ValueError(f"CrossEntropyLoss: z_loss must be >= 0, got {z_loss}")
+        if reduction not in _REDUCTIONS:
+            raise ValueError(f"CrossEntropyLoss: reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
+        self.ignore_index = ignore_index
+        self.label_smoothing = label_smoothing
+        self.z_loss = z_loss
+        self.reduction = reduction
+
+    def extra_repr(self) -> str:
+        return (f"ignore_index={self.ignore_index}, label_smoothing={self.label_smoothing}, "
+                f"z_loss={self.z_loss}, reduction={self.reduction!r}")
+
+    def forward(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        return cross_entropy(logits, target, self.ignore_index, label_smoothing=self.label_smoothing,
+                             z_loss=self.z_loss, reduction=self.reduction)

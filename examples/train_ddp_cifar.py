@@ -51,7 +51,12 @@ def train(rank, args):
     else:
         model = SimpleCNN().to(device)
     model = xddp.DDP(model, device_ids=[device.index] if use_fused else None)
-    criterion = nn.CrossEntropyLoss()
+    if args.fused_loss:  # the package's own loss kernels (ops/cross_entropy.py); torch's on CPU tensors
+        from distributeddataparallel_amd.ops import CrossEntropyLoss
+
+        criterion = CrossEntropyLoss()
+    else:
+        criterion = nn.CrossEntropyLoss()
     optimizer = torch.optim.SGD(model.parameters(), lr=args.lr)
     start_epoch = 0
     if args.resume and os.path.exists(args.resume):
@@ -135,6 +140,9 @@ def main():
     ap.add_argument("--accurate-convs", action="store_true",
                     help="MIOpen's implicit-GEMM fp32 conv solvers off: fp32-accurate weight gradients, slower "
                          "channels_last convs (utils/precision.py)")
+    ap.add_argument("--fused-loss", action="store_true",
+                    help="CrossEntropyLoss from this package (HIP kernels on the fp32 [batch, 10] logits) instead "
+                         "of nn.CrossEntropyLoss")
     ap.add_argument("--impl", choices=["xddp", "torch"], default="xddp",
                     help="torch = torch DDP + torch BatchNorm (the reference stack), for parity runs")
     args = ap.parse_args()

@@ -157,6 +157,21 @@ std::vector<at::Tensor> cross_entropy_rows_forward(const at::Tensor& logits, con
 at::Tensor cross_entropy_rows_backward(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& lse,
                                        const at::Tensor& g, const c10::optional<at::Tensor>& count,
                                        int64_t ignore_index, double label_smoothing, double z_loss);
+// cross_entropy_mixed.hip: the same against a two-label target (Mixup / CutMix): int64 a, b [R] weighted
+// lam and 1 - lam, lam fp32 on the device with 1 or R elements
+std::vector<at::Tensor> cross_entropy_mixed_forward(const at::Tensor& logits, const at::Tensor& a,
+                                                    const at::Tensor& b, const at::Tensor& lam, int64_t ignore_index,
+                                                    double label_smoothing, double z_loss, int64_t reduction,
+                                                    const at::Tensor& bad);
+at::Tensor cross_entropy_mixed_backward(const at::Tensor& logits, const at::Tensor& a, const at::Tensor& b,
+                                        const at::Tensor& lam, const at::Tensor& lse, const at::Tensor& g,
+                                        const c10::optional<at::Tensor>& count, int64_t ignore_index,
+                                        double label_smoothing, double z_loss);
+// mixup.hip: out[i] = x[partner[i]] inside box (y0, y1, x0, x1), x[i] outside; with an empty box
+// lam x[i] + (1 - lam) x[partner[i]]. x [B, C, H, W] dense NCHW / NHWC; lam fp32 [1 | B], box int32 [1 | B, 4]
+// and partner int32 [B] (default: B - 1 - i) on the device
+at::Tensor mix_images(const at::Tensor& x, const c10::optional<at::Tensor>& partner, const at::Tensor& lam,
+                      const at::Tensor& box);
 
 }  // namespace kernels
 }  // namespace xddp

@@ -38,6 +38,13 @@ void bind_norm_kernels(py::module_& m) {
   m.def("cross_entropy_rows_backward", &cross_entropy_rows_backward, py::arg("logits"), py::arg("target"),
         py::arg("lse"), py::arg("g"), py::arg("count"), py::arg("ignore_index"), py::arg("label_smoothing"),
         py::arg("z_loss"));
+  m.def("cross_entropy_mixed_forward", &cross_entropy_mixed_forward, py::arg("logits"), py::arg("a"), py::arg("b"),
+        py::arg("lam"), py::arg("ignore_index"), py::arg("label_smoothing"), py::arg("z_loss"), py::arg("reduction"),
+        py::arg("bad"));
+  m.def("cross_entropy_mixed_backward", &cross_entropy_mixed_backward, py::arg("logits"), py::arg("a"), py::arg("b"),
+        py::arg("lam"), py::arg("lse"), py::arg("g"), py::arg("count"), py::arg("ignore_index"),
+        py::arg("label_smoothing"), py::arg("z_loss"));
+  m.def("mix_images", &mix_images, py::arg("x"), py::arg("partner"), py::arg("lam"), py::arg("box"));
   m.def("bn_grad_partials", &bn_grad_partials, py::arg("dy"), py::arg("x"), py::arg("mean"));
   m.def("conv3x3_forward", &conv3x3_forward, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("stats"));
   m.def("conv3x3_rot_weight", &conv3x3_rot_weight, py::arg("w"));

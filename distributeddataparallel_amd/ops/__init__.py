@@ -5,4 +5,4 @@ from .layer_norm import FusedLayerNorm, FusedRMSNorm, layer_norm, rms_norm  # no
 from .pool import FusedMaxPool2d  # noqa: F401
 from .conv_bn import conv1x1_bn_act, conv3x3_bn_relu  # noqa: F401
 # ``ops.cross_entropy`` stays the module (its function is ``ops.cross_entropy.cross_entropy``)
-from .cross_entropy import CrossEntropyLoss  # noqa: F401
+from .cross_entropy import CrossEntropyLoss, MixedTarget  # noqa: F401

@@ -51,7 +51,12 @@ def train(rank, args):
     else:
         model = SimpleCNN().to(device)
     model = xddp.DDP(model, device_ids=[device.index] if use_fused else None)
-    if args.fused_loss:  # the package's own loss kernels (ops/cross_entropy.py); torch's on CPU tensors
+    mixer = None
+    if args.mixup > 0 or args.cutmix > 0:  # data/mixup.py: the batch is mixed on the device, the loss takes two labels
+        from distributeddataparallel_amd.data import Mixup
+
+        mixer = Mixup(mixup_alpha=args.mixup, cutmix_alpha=args.cutmix, seed=dist.get_rank())
+    if args.fused_loss or mixer is not None:  # the package's own loss kernels (ops/cross_entropy.py); torch's on CPU tensors
         from distributeddataparallel_amd.ops import CrossEntropyLoss
 
         criterion = CrossEntropyLoss()
@@ -71,6 +76,8 @@ def train(rank, args):
             if use_fused:
                 data = data.contiguous(memory_format=torch.channels_last)
             target = target.to(device, non_blocking=True)
+            if mixer is not None:
+                data, target = mixer(data, target)
             optimizer.zero_grad()
             loss = criterion(model(data), target)
             loss.backward()
@@ -143,6 +150,11 @@ def main():
     ap.add_argument("--fused-loss", action="store_true",
                     help="CrossEntropyLoss from this package (HIP kernels on the fp32 [batch, 10] logits) instead "
                          "of nn.CrossEntropyLoss")
+    ap.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
+                    help="Mixup with lam ~ Beta(ALPHA, ALPHA) (data/mixup.py); implies --fused-loss. 0 = off")
+    ap.add_argument("--cutmix", type=float, default=0.0, metavar="ALPHA",
+                    help="CutMix with lam ~ Beta(ALPHA, ALPHA); with --mixup each batch picks one of the two. "
+                         "Implies --fused-loss. 0 = off")
     ap.add_argument("--impl", choices=["xddp", "torch"], default="xddp",
                     help="torch = torch DDP + torch BatchNorm (the reference stack), for parity runs")
     args = ap.parse_args()

@@ -12,6 +12,7 @@
 #include "comm/peer.h"
 #include "kernels/multi_tensor.h"
 #include "kernels/norm.h"
+#include "kernels/q8_comm.h"
 #include "reducer/reducer.h"
 #include "store/tcp_store.h"
 
@@ -494,6 +495,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       py::arg("momentum"), py::arg("dampening"), py::arg("weight_decay"), py::arg("nesterov"), py::arg("maximize"),
       py::arg("first_step"), py::arg("trust_coefficient"), py::arg("eps"), py::arg("grad_scale") = py::none(),
       "LARS over a tensor list; returns the per-tensor trust ratios (fp32 [N], on the device)");
+
+  // 8-bit block-quantized gradient wire (kernels/q8_comm.hip), on the current stream
+  m.def("q8_quantize", &kernels::q8_quantize, py::arg("x"), py::arg("payload"), py::arg("block"),
+        py::arg("segments"), "payload (uint8) = `segments` segments of block codes and (lo, scale) pairs of flat x");
+  m.def("q8_dequantize_mean", &kernels::q8_dequantize_mean, py::arg("payload"), py::arg("out"), py::arg("block"),
+        py::arg("segments"), py::arg("mode"),
+        "out = mean over the segments (mode \"mean\") or their concatenation (mode \"concat\"), decoded");
+  m.def("q8_reduce_requant", &kernels::q8_reduce_requant, py::arg("payload_in"), py::arg("payload_out"),
+        py::arg("block"), py::arg("segments"), "payload_out (one segment) = quantize(mean of payload_in's segments)");
 
   // Topology of a captured HIP graph (hipGraph_t as an integer, e.g. torch.cuda.CUDAGraph(keep_graph=True)
   // .raw_cuda_graph()): (hipGraphNodeType of every node, edges as (from, to) node indices). Lets a test

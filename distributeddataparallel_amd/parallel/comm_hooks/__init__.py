@@ -28,6 +28,16 @@ def _lazy(modname, attr):
     return f
 
 
+def __getattr__(name):
+    # comm_hooks.Q8State / comm_hooks.q8_allreduce_hook, imported on first use like the hooks above;
+    # registered with ``model.register_comm_hook(Q8State(...), q8_allreduce_hook)``
+    if name in ("Q8State", "q8_allreduce_hook"):
+        from . import q8_hook
+
+        return getattr(q8_hook, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 class DDPCommHookType(Enum):
     ALLREDUCE = partial(_ddp_comm_hook_wrapper, comm_hook=default_hooks.allreduce_hook)
     FP16_COMPRESS = partial(_ddp_comm_hook_wrapper, comm_hook=default_hooks.fp16_compress_hook)

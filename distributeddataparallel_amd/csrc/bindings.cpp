@@ -495,6 +495,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       py::arg("momentum"), py::arg("dampening"), py::arg("weight_decay"), py::arg("nesterov"), py::arg("maximize"),
       py::arg("first_step"), py::arg("trust_coefficient"), py::arg("eps"), py::arg("grad_scale") = py::none(),
       "LARS over a tensor list; returns the per-tensor trust ratios (fp32 [N], on the device)");
+  m.def("fused_adafactor", [](const std::vector<at::Tensor>& p, const std::vector<at::Tensor>& g,
+                              const std::vector<at::Tensor>& row_vars, const std::vector<at::Tensor>& col_vars,
+                              const std::vector<at::Tensor>& variances, const std::vector<at::Tensor>& masters,
+                              double lr, double beta2_decay, double eps1, double eps2, double d, double wd,
+                              int64_t step, bool maximize, c10::optional<at::Tensor> gs) {
+        TORCH_CHECK(!p.empty(), "fused_adafactor: empty parameter list");
+        kernels::fused_adafactor(p, g, row_vars, col_vars, variances, masters, lr, beta2_decay, eps1, eps2, d, wd,
+                                 step, maximize, gs, stream_of(p[0]));
+      }, py::arg("params"), py::arg("grads"), py::arg("row_vars"), py::arg("col_vars"), py::arg("variances"),
+      py::arg("masters"), py::arg("lr"), py::arg("beta2_decay"), py::arg("eps1"), py::arg("eps2"), py::arg("d"),
+      py::arg("weight_decay"), py::arg("step"), py::arg("maximize"), py::arg("grad_scale") = py::none(),
+      "Adafactor over a list of matrices (row_vars, col_vars) or of vectors (variances)");
 
   // 8-bit block-quantized gradient wire (kernels/q8_comm.hip), on the current stream
   m.def("q8_quantize", &kernels::q8_quantize, py::arg("x"), py::arg("payload"), py::arg("block"),

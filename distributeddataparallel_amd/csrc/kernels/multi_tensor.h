@@ -115,5 +115,22 @@ at::Tensor fused_lars(const std::vector<at::Tensor>& params, const std::vector<a
                       bool first_step, double trust_coefficient, double eps,
                       const c10::optional<at::Tensor>& grad_scale, hipStream_t stream);
 
+// Adafactor (kernels/adafactor.hip; torch.optim.Adafactor semantics) over a list of whole, contiguous
+// tensors: either all of dim >= 2 (`row_vars` [..., R, 1] and `col_vars` [..., 1, C] given, factored
+// over the last two dims) or all of dim <= 1 (`variances` given). With t = step, omb = t^beta2_decay,
+// rho = min(lr, 1 / sqrt(t)), g' = g * grad_scale * (maximize ? -1 : 1) and w the fp32 master (if
+// `masters` is non-empty; the parameter then receives the rounded master) or the parameter:
+//   row_var <- lerp(row_var, mean_j g'^2, omb), col_var <- lerp(col_var, mean_i g'^2, omb),
+//   var = row_var col_var / max(mean_i row_var, eps1)      (dim <= 1: var = variance <- lerp(variance, g'^2, omb))
+//   u = g' rsqrt(max(var, eps1^2)),  alpha = max(eps2, RMS(w)) rho,
+//   w <- w (1 - lr weight_decay) - alpha / max(1, RMS(u) / d) u.
+// A fixed number of stream-ordered launches per table of 40 tensors, no host synchronisation; every
+// partial sum has its own slot and a fixed fold order, so a tensor's result does not depend on the list.
+void fused_adafactor(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
+                     const std::vector<at::Tensor>& row_vars, const std::vector<at::Tensor>& col_vars,
+                     const std::vector<at::Tensor>& variances, const std::vector<at::Tensor>& masters, double lr,
+                     double beta2_decay, double eps1, double eps2, double d, double weight_decay, int64_t step,
+                     bool maximize, const c10::optional<at::Tensor>& grad_scale, hipStream_t stream);
+
 }  // namespace kernels
 }  // namespace xddp

@@ -1,3 +1,4 @@
 from .fused import (FusedAdam, FusedAdamW, FusedSGD, clip_grad_norm_, grad_norm,  # noqa: F401
                     stochastic_round_bf16)
+from .adafactor import FusedAdafactor  # noqa: F401
 from .layerwise import FusedLAMB, FusedLARS  # noqa: F401

@@ -31,8 +31,10 @@ def _trust(ok_num, ok_den, value):
     return torch.where((ok_num != 0) & (ok_den != 0), value, torch.ones_like(value))
 
 
-class _LayerWise(_KeepStateDtypes, Optimizer):
-    """What the two classes share: whole-parameter stepping and the record of the last ratios."""
+class _WholeParams(_KeepStateDtypes, Optimizer):
+    """Stepping of whole parameters (``step``, ``step_params``; no ``advance`` / ``step_slices``) with every
+    refusal raised before any state changes, and fp32 masters: what the layer-wise optimizers and
+    ``FusedAdafactor`` share. A subclass supplies ``_step_group(group, [(param, grad)], grad_scale)``."""
 
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
@@ -64,7 +66,7 @@ class _LayerWise(_KeepStateDtypes, Optimizer):
                 loss = closure()
         work = [(group, [(p, p.grad) for p in group["params"] if p.grad is not None]) for group in self.param_groups]
         self._check(work)
-        self._ratios = {}
+        self._begin(True)
         for group, items in work:
             self._step_group(group, items, grad_scale)
         return loss
@@ -81,10 +83,27 @@ class _LayerWise(_KeepStateDtypes, Optimizer):
                 per_group[gi].append((p, g if g.shape == p.shape else g.view_as(p)))
         work = [(self.param_groups[gi], items) for gi, items in per_group.items()]
         self._check(work)
-        if not hasattr(self, "_ratios"):
-            self._ratios = {}
+        self._begin(False)
         for group, items in work:
             self._step_group(group, items, None)
+
+    def _begin(self, whole_step):
+        pass
+
+    def _master(self, p, group):
+        st = self.state[p]
+        use = group["master_weights"] and p.dtype in _LOW
+        if use and "master" not in st:
+            st["master"] = p.detach().float().clone(memory_format=torch.preserve_format)
+        return use
+
+
+class _LayerWise(_WholeParams):
+    """What LAMB and LARS add: the record of the last trust ratios."""
+
+    def _begin(self, whole_step):
+        if whole_step or not hasattr(self, "_ratios"):
+            self._ratios = {}
 
     def trust_ratios(self) -> Dict[torch.Tensor, torch.Tensor]:
         """``{param: 0-dim fp32 tensor on the parameter's device}``: the ratio each parameter's last
@@ -94,13 +113,6 @@ class _LayerWise(_KeepStateDtypes, Optimizer):
     def _record(self, params, ratios):
         for p, r in zip(params, ratios.unbind(0) if torch.is_tensor(ratios) else ratios):
             self._ratios[p] = r
-
-    def _master(self, p, group):
-        st = self.state[p]
-        use = group["master_weights"] and p.dtype in _LOW
-        if use and "master" not in st:
-            st["master"] = p.detach().float().clone(memory_format=torch.preserve_format)
-        return use
 
 
 class FusedLAMB(_LayerWise):

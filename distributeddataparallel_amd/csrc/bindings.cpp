@@ -12,6 +12,7 @@
 #include "comm/peer.h"
 #include "kernels/multi_tensor.h"
 #include "kernels/norm.h"
+#include "kernels/powersgd.h"
 #include "kernels/q8_comm.h"
 #include "reducer/reducer.h"
 #include "store/tcp_store.h"
@@ -516,6 +517,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out = mean over the segments (mode \"mean\") or their concatenation (mode \"concat\"), decoded");
   m.def("q8_reduce_requant", &kernels::q8_reduce_requant, py::arg("payload_in"), py::arg("payload_out"),
         py::arg("block"), py::arg("segments"), "payload_out (one segment) = quantize(mean of payload_in's segments)");
+
+  // Fused PowerSGD (kernels/powersgd.hip), on the current stream
+  py::class_<kernels::PsgdPlan, std::shared_ptr<kernels::PsgdPlan>>(
+      m, "PsgdPlan", "launch tables and workspace of one list of [n, m] matrices with their E, P [n, r], Q [m, r]")
+      .def(py::init<const std::vector<at::Tensor>&, const std::vector<at::Tensor>&, const std::vector<at::Tensor>&,
+                    const std::vector<at::Tensor>&>(),
+           py::arg("mats"), py::arg("errors"), py::arg("ps"), py::arg("qs"))
+      .def("project", &kernels::PsgdPlan::project, "P = (G + E) Q")
+      .def("backproject", &kernels::PsgdPlan::backproject, "Q = (G + E)^T P")
+      .def("reconstruct", &kernels::PsgdPlan::reconstruct, py::arg("inv_world"),
+           "G <- round(inv_world P Q^T), E <- (G + E) - G_new")
+      .def("orthonormalize_p", &kernels::PsgdPlan::orthonormalize_p, py::arg("epsilon") = 0.0)
+      .def("orthonormalize_q", &kernels::PsgdPlan::orthonormalize_q, py::arg("epsilon") = 0.0)
+      .def("workspace_floats", &kernels::PsgdPlan::workspace_floats);
+  m.def("psgd_orthonormalize", &kernels::psgd_orthonormalize, py::arg("mats"), py::arg("epsilon") = 0.0,
+        "CholeskyQR2 of every [n, r] fp32 matrix of the list, in place");
 
   // Topology of a captured HIP graph (hipGraph_t as an integer, e.g. torch.cuda.CUDAGraph(keep_graph=True)
   // .raw_cuda_graph()): (hipGraphNodeType of every node, edges as (from, to) node indices). Lets a test

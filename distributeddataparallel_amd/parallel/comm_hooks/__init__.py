@@ -17,6 +17,14 @@ def _powerSGD_comm_hook_wrapper(comm_hook, model, state, matrix_approximation_ra
     model.register_comm_hook(st, comm_hook)
 
 
+def _fused_powerSGD_comm_hook_wrapper(comm_hook, model, state, matrix_approximation_rank, start_powerSGD_iter=1_000):
+    from .powersgd_fused_hook import FusedPowerSGDState
+
+    st = FusedPowerSGDState(process_group=state, matrix_approximation_rank=matrix_approximation_rank,
+                            start_powerSGD_iter=start_powerSGD_iter)
+    model.register_comm_hook(st, comm_hook)
+
+
 def _lazy(modname, attr):
     def f(*a, **k):
         import importlib
@@ -35,6 +43,10 @@ def __getattr__(name):
         from . import q8_hook
 
         return getattr(q8_hook, name)
+    if name in ("FusedPowerSGDState", "fused_powerSGD_hook"):
+        from . import powersgd_fused_hook
+
+        return getattr(powersgd_fused_hook, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -53,6 +65,9 @@ class DDPCommHookType(Enum):
     BATCHED_POWER_SGD = partial(_powerSGD_comm_hook_wrapper,
                                 comm_hook=_lazy("powerSGD_hook", "batched_powerSGD_hook"),
                                 matrix_approximation_rank=1)
+    FUSED_POWER_SGD = partial(_fused_powerSGD_comm_hook_wrapper,
+                              comm_hook=_lazy("powersgd_fused_hook", "fused_powerSGD_hook"),
+                              matrix_approximation_rank=1)
     NOOP = partial(_ddp_comm_hook_wrapper, comm_hook=debugging_hooks.noop_hook)
 
 

@@ -13,6 +13,7 @@
 #include "kernels/multi_tensor.h"
 #include "kernels/norm.h"
 #include "kernels/powersgd.h"
+#include "kernels/onebit_comm.h"
 #include "kernels/q8_comm.h"
 #include "reducer/reducer.h"
 #include "store/tcp_store.h"
@@ -517,6 +518,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out = mean over the segments (mode \"mean\") or their concatenation (mode \"concat\"), decoded");
   m.def("q8_reduce_requant", &kernels::q8_reduce_requant, py::arg("payload_in"), py::arg("payload_out"),
         py::arg("block"), py::arg("segments"), "payload_out (one segment) = quantize(mean of payload_in's segments)");
+
+  // 1-bit gradient wire with error feedback (kernels/onebit_comm.hip), on the current stream
+  m.def("onebit_compress", &kernels::onebit_compress, py::arg("x"), py::arg("err"), py::arg("payload"),
+        py::arg("block"), py::arg("segments"),
+        "payload (uint8) = `segments` segments of sign bits and block scales of x + err; err <- x + err - decoded");
+  m.def("onebit_decode_mean", &kernels::onebit_decode_mean, py::arg("payload"), py::arg("out"), py::arg("block"),
+        py::arg("segments"), py::arg("mode"),
+        "out = mean over the segments (mode \"mean\") or their concatenation (mode \"concat\"), decoded");
+  m.def("onebit_reduce_recompress", &kernels::onebit_reduce_recompress, py::arg("payload_in"), py::arg("err"),
+        py::arg("payload_out"), py::arg("block"), py::arg("segments"), py::arg("numel"),
+        "payload_out (one segment) = compress(mean of payload_in's segments + err), err updated in place");
 
   // Fused PowerSGD (kernels/powersgd.hip), on the current stream
   py::class_<kernels::PsgdPlan, std::shared_ptr<kernels::PsgdPlan>>(

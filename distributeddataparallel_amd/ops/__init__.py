@@ -6,5 +6,6 @@ from .pool import FusedMaxPool2d  # noqa: F401
 from .conv_bn import conv1x1_bn_act, conv3x3_bn_relu  # noqa: F401
 # ``ops.cross_entropy`` stays the module (its function is ``ops.cross_entropy.cross_entropy``)
 from .cross_entropy import CrossEntropyLoss, MixedTarget  # noqa: F401
+from . import onebit  # noqa: F401  (1-bit gradient wire with error feedback: ops.onebit.compress, ...)
 from . import powersgd  # noqa: F401  (fused PowerSGD step: ops.powersgd.project, ...)
 from . import q8  # noqa: F401  (8-bit block-quantized gradient wire: ops.q8.quantize, ...)

@@ -43,6 +43,10 @@ def __getattr__(name):
         from . import q8_hook
 
         return getattr(q8_hook, name)
+    if name in ("OneBitState", "onebit_allreduce_hook"):
+        from . import onebit_hook
+
+        return getattr(onebit_hook, name)
     if name in ("FusedPowerSGDState", "fused_powerSGD_hook"):
         from . import powersgd_fused_hook
 

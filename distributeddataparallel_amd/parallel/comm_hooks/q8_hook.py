@@ -84,6 +84,18 @@ def _then(fut, done, step):
     fut.then(callback)
 
 
+def _issue_in_order(state, issued, done, exchange):
+    """Run ``exchange`` (a bucket's first collective) once the bucket before it on ``state`` has
+    issued its second; the caller completes ``issued`` when this bucket has issued its own."""
+    # after a failure too: the next bucket must not wait for ever
+    done.add_done_callback(lambda _: issued.done() or issued.set_result(None))
+    before, state._issued = state._issued, issued
+    if before is None or before.done():
+        exchange()
+    else:
+        _then(before, done, exchange)
+
+
 def q8_allreduce_hook(state: Q8State, bucket) -> torch.futures.Future:
     pg = state.process_group if state.process_group is not None else xdist.get_default_group()
     w, block = pg.size(), state.block
@@ -119,15 +131,8 @@ def q8_allreduce_hook(state: Q8State, bucket) -> torch.futures.Future:
         issued.set_result(None)
         _then(fut, done, finish)
 
-    # after a failure too: the next bucket must not wait for ever
-    done.add_done_callback(lambda _: issued.done() or issued.set_result(None))
-
     def exchange():
         _then(pg.alltoall_base(recv, send).get_future(), done, gather)
 
-    before, state._issued = state._issued, issued
-    if before is None or before.done():
-        exchange()
-    else:
-        _then(before, done, exchange)
+    _issue_in_order(state, issued, done, exchange)
     return done

@@ -115,7 +115,7 @@ def wire_table(emit):
         emit(f"# {w:3d}   {8 * f:9.2f}   {4 * f:9.2f}   {(w - 1) * (1 + 8 / G):12.2f}   {2 * f * (1 + 8 / G):10.2f}")
 
 
-def resources(emit):
+def resources(emit, KERNEL=KERNEL):
     """VGPRs, LDS, scratch and occupancy per kernel, from the compiler's remarks."""
     from distributeddataparallel_amd._build import EXTRA_HIP_FLAGS
 

@@ -15,6 +15,7 @@
 #include "kernels/powersgd.h"
 #include "kernels/onebit_comm.h"
 #include "kernels/q8_comm.h"
+#include "kernels/topk_comm.h"
 #include "reducer/reducer.h"
 #include "store/tcp_store.h"
 
@@ -528,6 +529,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out = mean over the segments (mode \"mean\") or their concatenation (mode \"concat\"), decoded");
   m.def("onebit_reduce_recompress", &kernels::onebit_reduce_recompress, py::arg("payload_in"), py::arg("err"),
         py::arg("payload_out"), py::arg("block"), py::arg("segments"), py::arg("numel"),
+        "payload_out (one segment) = compress(mean of payload_in's segments + err), err updated in place");
+
+  // top-k sparsified gradient wire with error feedback (kernels/topk_comm.hip), on the current stream
+  m.def("topk_compress", &kernels::topk_compress, py::arg("x"), py::arg("err"), py::arg("payload"), py::arg("block"),
+        py::arg("k"), py::arg("segments"),
+        "payload (uint8) = `segments` segments of the k largest |x + err| per block; err <- x + err - decoded");
+  m.def("topk_decode_mean", &kernels::topk_decode_mean, py::arg("payload"), py::arg("out"), py::arg("block"),
+        py::arg("k"), py::arg("segments"), py::arg("mode"),
+        "out = mean over the segments (mode \"mean\") or their concatenation (mode \"concat\"), decoded");
+  m.def("topk_reduce_reselect", &kernels::topk_reduce_reselect, py::arg("payload_in"), py::arg("err"),
+        py::arg("payload_out"), py::arg("block"), py::arg("k"), py::arg("segments"), py::arg("numel"),
         "payload_out (one segment) = compress(mean of payload_in's segments + err), err updated in place");
 
   // Fused PowerSGD (kernels/powersgd.hip), on the current stream

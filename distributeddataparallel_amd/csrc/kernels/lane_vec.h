@@ -1,4 +1,5 @@
-// Lane-private runs of a flat bucket for the gradient-wire kernels (q8_comm.hip, onebit_comm.hip):
+// Lane-private runs of a flat bucket for the gradient-wire kernels (q8_comm.hip, onebit_comm.hip,
+// topk_comm.hip):
 // one wave owns one block of the format, a lane holds E consecutive elements of it in registers.
 #pragma once
 

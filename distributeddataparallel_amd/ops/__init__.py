@@ -9,3 +9,4 @@ from .cross_entropy import CrossEntropyLoss, MixedTarget  # noqa: F401
 from . import onebit  # noqa: F401  (1-bit gradient wire with error feedback: ops.onebit.compress, ...)
 from . import powersgd  # noqa: F401  (fused PowerSGD step: ops.powersgd.project, ...)
 from . import q8  # noqa: F401  (8-bit block-quantized gradient wire: ops.q8.quantize, ...)
+from . import topk  # noqa: F401  (top-k sparsified gradient wire with error feedback: ops.topk.compress, ...)

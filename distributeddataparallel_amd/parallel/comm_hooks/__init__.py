@@ -47,6 +47,10 @@ def __getattr__(name):
         from . import onebit_hook
 
         return getattr(onebit_hook, name)
+    if name in ("TopKState", "topk_allreduce_hook"):
+        from . import topk_hook
+
+        return getattr(topk_hook, name)
     if name in ("FusedPowerSGDState", "fused_powerSGD_hook"):
         from . import powersgd_fused_hook
 

@@ -172,6 +172,13 @@ at::Tensor cross_entropy_mixed_backward(const at::Tensor& logits, const at::Tens
 // and partner int32 [B] (default: B - 1 - i) on the device
 at::Tensor mix_images(const at::Tensor& x, const c10::optional<at::Tensor>& partner, const at::Tensor& lam,
                       const at::Tensor& box);
+// dwconv.hip: depthwise k x k conv (k in 3, 5, 7; stride 1, padding k / 2) on dense channels_last x
+// [B, C, H, W], C % 8 == 0, fp32 / bf16 / fp16. w_taps is the weight tap-major [k * k, C]; flip reverses
+// the taps (the input gradient: dx = dwconv_forward(dy, w_taps, none, true)). dwconv_wgrad returns
+// {dw [C, 1, k, k], db [C] or undefined}, bitwise repeatable.
+at::Tensor dwconv_forward(const at::Tensor& x, const at::Tensor& w_taps, const c10::optional<at::Tensor>& bias,
+                          bool flip);
+std::vector<at::Tensor> dwconv_wgrad(const at::Tensor& dy, const at::Tensor& x, int64_t k, bool need_bias);
 
 }  // namespace kernels
 }  // namespace xddp

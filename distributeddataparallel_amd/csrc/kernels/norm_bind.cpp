@@ -45,7 +45,10 @@ void bind_norm_kernels(py::module_& m) {
         py::arg("lam"), py::arg("lse"), py::arg("g"), py::arg("count"), py::arg("ignore_index"),
         py::arg("label_smoothing"), py::arg("z_loss"));
   m.def("mix_images", &mix_images, py::arg("x"), py::arg("partner"), py::arg("lam"), py::arg("box"));
-  m.def("bn_grad_partials", &bn_grad_partials, py::arg("dy"), py::arg("x"), py::arg("mean"));
+  m.def("dwconv_forward", &dwconv_forward, py::arg("x"), py::arg("w_taps"), py::arg("bias") = py::none(),
+        py::arg("flip") = false);
+  m.def("dwconv_wgrad", &dwconv_wgrad, py::arg("dy"), py::arg("x"), py::arg("k"), py::arg("need_bias"));
+  m.def("bn_grad_partials",&bn_grad_partials, py::arg("dy"), py::arg("x"), py::arg("mean"));
   m.def("conv3x3_forward", &conv3x3_forward, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("stats"));
   m.def("conv3x3_rot_weight", &conv3x3_rot_weight, py::arg("w"));
   m.def("conv3x3_rot_weights", &conv3x3_rot_weights, py::arg("ws"));

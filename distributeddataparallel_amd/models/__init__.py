@@ -1,4 +1,5 @@
 """Model zoo: the reference's ResNet-18/CIFAR head plus the BASELINE.json north-star configs."""
+from .convnext import ConvNeXt, convnext_tiny  # noqa: F401
 from .llama import Llama, LlamaConfig, llama3_8b, llama_tiny  # noqa: F401
 from .mlp import MLP  # noqa: F401
 from .resnet import (  # noqa: F401

@@ -140,7 +140,7 @@ def bench_loss(rows, C, dtype, rounds, emit):
     check_targets(block=True)
 
 
-def resources(emit):
+def resources(emit, kernels=None, extra_flags=()):
     """VGPRs, LDS, scratch and occupancy per kernel, from the compiler's remarks."""
     ninja = "distributeddataparallel_amd/build/build.ninja"
     if not (os.path.exists(ninja) and os.path.exists("/opt/rocm/bin/hipcc")):
@@ -150,8 +150,8 @@ def resources(emit):
     emit("# kernel resources (hipcc -Rpass-analysis=kernel-resource-usage)")
     keys = {"VGPRs": "vgpr", "VGPRs Spill": "spill", "LDS Size [bytes/block]": "lds", "ScratchSize [bytes/lane]": "scratch",
             "Occupancy [waves/SIMD]": "occ"}
-    for src in KERNELS:
-        err = subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-c", src, "-o", os.devnull,
+    for src in kernels or KERNELS:
+        err = subprocess.run(["/opt/rocm/bin/hipcc", *flags, *extra_flags, "-c", src, "-o", os.devnull,
                               "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True).stderr
         cur, rows = None, []
         for line in err.splitlines():

@@ -179,6 +179,15 @@ at::Tensor mix_images(const at::Tensor& x, const c10::optional<at::Tensor>& part
 at::Tensor dwconv_forward(const at::Tensor& x, const at::Tensor& w_taps, const c10::optional<at::Tensor>& bias,
                           bool flip);
 std::vector<at::Tensor> dwconv_wgrad(const at::Tensor& dy, const at::Tensor& x, int64_t k, bool need_bias);
+// window_attn.hip: softmax(scale q k^T + bias, masked where labels differ) v inside windows of N <= 64
+// tokens. qkv dense bf16 [Bw, N, 3, H, 32]; bias [H, N, N] bf16 / fp32; labels int32 [nW, N], window w
+// uses row w % nW. Forward returns o [Bw, N, H, 32]; backward returns {dqkv (qkv's layout), dbias (bias's
+// dtype) or undefined}, recomputing the softmax from qkv, bias and labels; bitwise repeatable.
+at::Tensor window_attn_forward(const at::Tensor& qkv, const c10::optional<at::Tensor>& bias,
+                               const c10::optional<at::Tensor>& labels, double scale);
+std::vector<at::Tensor> window_attn_backward(const at::Tensor& qkv, const c10::optional<at::Tensor>& bias,
+                                             const c10::optional<at::Tensor>& labels, const at::Tensor& d_out,
+                                             double scale, bool need_dbias);
 
 }  // namespace kernels
 }  // namespace xddp

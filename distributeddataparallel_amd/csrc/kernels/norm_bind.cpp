@@ -48,6 +48,10 @@ void bind_norm_kernels(py::module_& m) {
   m.def("dwconv_forward", &dwconv_forward, py::arg("x"), py::arg("w_taps"), py::arg("bias") = py::none(),
         py::arg("flip") = false);
   m.def("dwconv_wgrad", &dwconv_wgrad, py::arg("dy"), py::arg("x"), py::arg("k"), py::arg("need_bias"));
+  m.def("window_attn_forward", &window_attn_forward, py::arg("qkv"), py::arg("bias"), py::arg("labels"),
+        py::arg("scale"));
+  m.def("window_attn_backward", &window_attn_backward, py::arg("qkv"), py::arg("bias"), py::arg("labels"),
+        py::arg("d_out"), py::arg("scale"), py::arg("need_dbias"));
   m.def("bn_grad_partials",&bn_grad_partials, py::arg("dy"), py::arg("x"), py::arg("mean"));
   m.def("conv3x3_forward", &conv3x3_forward, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("stats"));
   m.def("conv3x3_rot_weight", &conv3x3_rot_weight, py::arg("w"));

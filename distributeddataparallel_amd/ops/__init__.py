@@ -5,6 +5,7 @@ from .layer_norm import FusedLayerNorm, FusedRMSNorm, layer_norm, rms_norm  # no
 from .pool import FusedMaxPool2d  # noqa: F401
 from .conv_bn import conv1x1_bn_act, conv3x3_bn_relu  # noqa: F401
 from .dwconv import DepthwiseConv2d, depthwise_conv2d  # noqa: F401
+from .window_attention import WindowAttention, window_attention, window_attention_supported  # noqa: F401
 # ``ops.cross_entropy`` stays the module (its function is ``ops.cross_entropy.cross_entropy``)
 from .cross_entropy import CrossEntropyLoss, MixedTarget  # noqa: F401
 from . import onebit  # noqa: F401  (1-bit gradient wire with error feedback: ops.onebit.compress, ...)
